@@ -20,6 +20,14 @@ r, r+N, ...), the reference's byte-range / stripe splitting
 -- with no data-path collective (weak scaling); the only cross-rank traffic is
 the timing barrier, one max-reduce and the per-rank report, on gloo (host).
 
+A plain run does what `value` needs and no more: set up, warm up, time the K
+steps (ms_per_step = their wall time / K), write the outputs if asked
+(--dump-outputs DIR) and print the line.  Everything else the line can carry
+-- the self-check against the other multiply engine, the copy ceiling and XOR
+probe, the configs block, the sharded C5 job, the PCIe-inclusive e2e rates and
+the CPU baselines that also check the GPU's stripe -- runs after the timed
+steps under --full only, and is null in a plain run's line.
+
 Launch:
     python bench.py                                  N = 1, in process
     python bench.py --gpus N                         spawns N rank processes
@@ -71,15 +79,31 @@ def parse(argv=None):
                          "plateaus from 96, DESIGN.md §6; C5 8 x 256 MiB)")
     ap.add_argument("--kernel", choices=["perm", "lds"], default="perm")
     ap.add_argument("--nt", type=int, default=1, help="non-temporal loads/stores")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the self-check "
+                         "against the other multiply engine, the copy ceiling and XOR probe, the per-config block, "
+                         "the sharded C5 job, the PCIe-inclusive e2e rates and the CPU baselines (which also check "
+                         "the GPU's stripe).  Without it the run sets up, warms up, times the steps and prints the "
+                         "line, with those entries null; --cpu-seconds, --no-configs and --e2e-stripes then have "
+                         "no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last step left in HBM (the parity shards and, with a "
+                         "decode, the rebuilt shards) as DIR/<name>.npy in float32: a fixed seeded sample of bytes "
+                         "plus the first and last bytes of every shard (dump_outputs); the inputs are seeded, so two "
+                         "builds run with the same arguments compare output for output")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0,
+                    help="--full: CPU baseline sample budget (0 = skip)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the per-config block (C2 / C3 / C4 / C5 launches; run by every rank on its own GPU "
-                         "at any N)")
+                    help="--full: skip the per-config block (C2 / C3 / C4 / C5 launches; run by every rank on its "
+                         "own GPU at any N)")
     ap.add_argument("--e2e-stripes", type=int, default=24,
-                    help="pinned host stripes for the PCIe-inclusive e2e rate on rank 0 (0 = skip)")
+                    help="--full: pinned host stripes for the PCIe-inclusive e2e rate on rank 0 (0 = skip)")
     ap.add_argument("--spawn-selftest", action="store_true",
                     help="launch / rendezvous / report path only, no GPU work (CPU test of --gpus N)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------ launch ----
@@ -837,6 +861,56 @@ def config_block(E, N, dev, stream, kind, nt, main=None):
     return out
 
 
+# ------------------------------------------------------------ output dump ----
+DUMP_SEED = 0xD0C5
+DUMP_SAMPLE_BYTES = 4 << 20  # sampled bytes per array (as float32: 16 MiB)
+DUMP_EDGE_BYTES = 4096       # leading and trailing bytes of every shard
+
+
+def dump_indices(B: int, n_sh: int, S: int, n: int, seed: int):
+    """`n` sorted flat positions (seeded, with repeats) in a [B, n_sh, S] byte
+    array, as (stripe, shard, offset) index arrays.  Pure: tested on CPU."""
+    import numpy as np
+    flat = np.sort(np.random.default_rng(seed).integers(0, B * n_sh * S, size=n, dtype=np.int64))
+    return flat // (n_sh * S), (flat // S) % n_sh, flat % S
+
+
+def dump_outputs(out_dir: str, slab, shard_ids: dict, S: int, rank: int, world: int) -> dict:
+    """Write the bytes the last timed step left in the slab's output shards
+    (`shard_ids`: name -> the shard indices, e.g. parity -> k..k+m-1) as
+    float32 .npy files under `out_dir`, one value per byte:
+      <name>_sample.npy  DUMP_SAMPLE_BYTES seeded positions over all stripes
+                         (the whole array when it is no larger)
+      <name>_edges.npy   [B, shards, 2 * DUMP_EDGE_BYTES]: the first and last
+                         bytes of every shard, where a tail bug would sit
+    At N > 1 every rank writes its own stripes as <name>_..._rank<r>.npy.
+    Returns {file name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    B, dev = slab.shape[0], slab.device
+    suffix = f"_rank{rank}" if world > 1 else ""
+    written = {}
+
+    def save(name, t):
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        written[f"{name}{suffix}.npy"] = list(a.shape)
+
+    for n, (name, ids) in enumerate(sorted(shard_ids.items())):
+        sel = slab[:, ids, :S]  # [B, len(ids), S]; advanced indexing on dim 1 copies
+        if sel.numel() <= DUMP_SAMPLE_BYTES:
+            save(f"{name}_sample", sel.reshape(-1))
+        else:
+            b, i, o = (torch.from_numpy(x).to(dev) for x in dump_indices(B, len(ids), S, DUMP_SAMPLE_BYTES,
+                                                                        DUMP_SEED + n))
+            save(f"{name}_sample", sel[b, i, o])
+        e = min(DUMP_EDGE_BYTES, S)
+        save(f"{name}_edges", torch.cat([sel[:, :, :e], sel[:, :, S - e:]], dim=2))
+        del sel
+    return written
+
+
 # -------------------------------------------------------------------- main ----
 def selftest_main(args):
     """--spawn-selftest: the multi-rank control path without a GPU."""
@@ -1017,23 +1091,40 @@ def main(argv=None):
     user_per_stripe = (2 if erasures else 1) * k * S
     value = world * args.steps * B * user_per_stripe / t / 2**30
 
+    dumped = None
+    if args.dump_outputs:  # before anything below overwrites the slab
+        outputs = {"parity": list(range(k, k + m))}
+        if erasures:
+            outputs["rebuilt"] = list(erasures)
+        dumped = dump_outputs(args.dump_outputs, slab, outputs, S, rank, world)
+
+    # a plain run stops here: everything below that launches, copies or runs
+    # on the CPU is --full's
+    full = args.full
+    no_configs = args.no_configs or not full
+    cpu_seconds = args.cpu_seconds if full else 0.0
+    e2e_stripes = args.e2e_stripes if full else 0
+
     # independent check of the timed result on every rank: stripe 0 re-encoded
     # with the OTHER multiply engine (LDS nibble tables, gf_apply_lds), outside
     # the timed region and its statistics
-    chk = torch.empty((m, S), dtype=torch.uint8, device=dev)
-    ref = E.encode_plan(k, m, M, local).bind([shards[0][:k]], [[chk[i] for i in range(m)]], S)
-    ref.set_kernel(N.KERNEL_LDS if kind == N.KERNEL_PERM else N.KERNEL_PERM, True)
-    ref.launch(stream.cuda_stream)
-    torch.cuda.synchronize(dev)
-    ok = all(bool(torch.equal(chk[i], shards[0][k + i])) for i in range(m))
+    ok = None
+    if full:
+        chk = torch.empty((m, S), dtype=torch.uint8, device=dev)
+        ref = E.encode_plan(k, m, M, local).bind([shards[0][:k]], [[chk[i] for i in range(m)]], S)
+        ref.set_kernel(N.KERNEL_LDS if kind == N.KERNEL_PERM else N.KERNEL_PERM, True)
+        ref.launch(stream.cuda_stream)
+        torch.cuda.synchronize(dev)
+        ok = all(bool(torch.equal(chk[i], shards[0][k + i])) for i in range(m))
+        del ref
     # rank 0's stripe 0 for the CPU baseline (taken at every N: SURVEY.md §8d,
     # the reference CPU path timed in the same run)
-    host_stripe = slab[0, :, :S].cpu().numpy() if (rank == 0 and args.cpu_seconds > 0) else None
+    host_stripe = slab[0, :, :S].cpu().numpy() if (rank == 0 and cpu_seconds > 0) else None
 
     enc_bytes = (k + m) * S * B  # algorithmic HBM bytes per encode launch
     dec_bytes = (k + len(erasures)) * S * B if erasures else 0  # k survivors read + erased shards written
     main_entries = {}
-    if not args.no_configs and args.config == "C3":
+    if not no_configs and args.config == "C3":
         e = {"workload": f"RS(10,4) encode, 4 MiB shards, {B} stripes (the timed steps)"}
         e.update(roofline_entry(enc_bytes, enc_ms))
         main_entries["C3_encode"] = e
@@ -1041,9 +1132,10 @@ def main(argv=None):
         e.update(roofline_entry(dec_bytes, dec_ms))
         main_entries["C3_decode_0"] = e
         main_entries.update(c3_decode_shapes(E, shards, S, B, dev, stream, kind, bool(args.nt)))
-    del enc, dec, ref
-    copy = copy_ceiling(slab, S)  # after the parity checks: the copy overwrites the slab's second half
-    mix = xor_stream_probe(slab, S, k, m)  # overwrites the parity shards
+    del enc, dec
+    # after the parity checks: the copy overwrites the slab's second half, the probe the parity shards
+    copy = copy_ceiling(slab, S) if full else None
+    mix = xor_stream_probe(slab, S, k, m) if full else None
     if main_entries:
         with_mix(main_entries["C3_encode"], mix)
         mix_dec = xor_stream_probe(slab, S, k, 1)  # every C3 decode shape reads 10 shards and writes 1
@@ -1052,18 +1144,18 @@ def main(argv=None):
     # diagnostics only (A/B of the N > 1 e2e leg): ECGPU_BENCH_SKIP=configs,c5 drops those blocks
     skip = set(filter(None, os.environ.get("ECGPU_BENCH_SKIP", "").split(",")))
     configs = None
-    if not args.no_configs and "configs" not in skip:
+    if not no_configs and "configs" not in skip:
         del shards
         slab = None
         torch.cuda.empty_cache()
         configs = config_block(E, N, dev, stream, kind, bool(args.nt), main_entries)
     c5 = None
-    if not args.no_configs and args.config == "C3" and "c5" not in skip:
+    if not no_configs and args.config == "C3" and "c5" not in skip:
         c5 = sharded_c5(E, N, dev, stream, kind, bool(args.nt), rank, world)
     # about 1.5 GiB of pinned host memory per rank at most (C3: 24 stripes, C5: 6)
-    e2e_n = min(args.e2e_stripes, max(2, (3 << 29) // ((k + m) * S)))
+    e2e_n = min(e2e_stripes, max(2, (3 << 29) // ((k + m) * S)))
     e2e_mine = None
-    if world > 1 and args.e2e_stripes > 0:
+    if world > 1 and e2e_stripes > 0:
         repeats = []
         for _ in range(max(1, int(os.environ.get("ECGPU_BENCH_E2E_REPEAT", "1") or 1))):  # diagnostics: >1 repeats
             barrier(world)
@@ -1095,7 +1187,9 @@ def main(argv=None):
     mine["cpu_fallbacks"] = N.fallback_count()
     mine["cpu_calls"] = N.cpu_call_count()
     per_rank = gather(mine, world)
-    ok = (all(p["parity_ok"] for p in per_rank) and (c5 is None or c5["parity_ok"]) and
+    # parity_ok is None where the self-check did not run (a plain run): only a failed check fails the run
+    parity_ok = all(p["parity_ok"] for p in per_rank) if full else None
+    ok = (parity_ok is not False and (c5 is None or c5["parity_ok"]) and
           all(p["cpu_fallbacks"] == 0 and p["cpu_calls"] == 0 for p in per_rank))
     devices_ok, devices_note = distinct_devices(per_rank, rehearsal)
     barrier(world)  # every rank's GPU work is done: the CPU baseline below runs alone
@@ -1105,21 +1199,21 @@ def main(argv=None):
     if rank == 0:
         cpu = cpu_share = cpu_all = cpu_o3 = None
         if host_stripe is not None:
-            cpu, cpu_ok = cpu_baseline(args.cpu_seconds, host_stripe, k, m, erasures)
+            cpu, cpu_ok = cpu_baseline(cpu_seconds, host_stripe, k, m, erasures)
             share = host_cpus()
-            cpu_share, ok_share = cpu_baseline(max(2.0, args.cpu_seconds / 2), host_stripe, k, m, erasures,
+            cpu_share, ok_share = cpu_baseline(max(2.0, cpu_seconds / 2), host_stripe, k, m, erasures,
                                                threads=len(share), cpus=share)
             cpu_ok = cpu_ok and ok_share
             every = all_host_cpus()
             if len(every) > len(share):  # a whole host (the 8-GPU node): every core it gives us
-                cpu_all, ok_all = cpu_baseline(max(2.0, args.cpu_seconds / 2), host_stripe, k, m, erasures,
+                cpu_all, ok_all = cpu_baseline(max(2.0, cpu_seconds / 2), host_stripe, k, m, erasures,
                                                threads=len(every), cpus=every)
                 cpu_ok = cpu_ok and ok_all
             else:  # a one-GPU lease: its share is all there is
                 cpu_all = dict(cpu_share, note="the per-GPU share is every CPU this process may use here")
             from oracle.oracle import REFERENCE_O3_SO
             if host_has_avx2() and os.path.exists(REFERENCE_O3_SO):
-                cpu_o3, ok_o3 = cpu_baseline(max(2.0, args.cpu_seconds / 2), host_stripe, k, m, erasures, o3=True)
+                cpu_o3, ok_o3 = cpu_baseline(max(2.0, cpu_seconds / 2), host_stripe, k, m, erasures, o3=True)
                 cpu_ok = cpu_ok and ok_o3
         e2e_per_rank = e2e_agg = None
         if world > 1:
@@ -1127,7 +1221,7 @@ def main(argv=None):
             e2e = e2e_per_rank[0]
             e2e_agg = e2e_aggregate(e2e_per_rank) if all(e2e_per_rank) else None
         else:
-            e2e = e2e_host_pipelines(E, M, k, m, S, erasures, dev, stripes=e2e_n) if args.e2e_stripes > 0 else None
+            e2e = e2e_host_pipelines(E, M, k, m, S, erasures, dev, stripes=e2e_n) if e2e_stripes > 0 else None
         e2e_ok = (None if not e2e else
                   all(bool(r["encode"]["parity_ok"] and r.get("decode", {}).get("rebuilt_ok", True))
                       for r in (e2e_per_rank or [e2e])))
@@ -1156,6 +1250,8 @@ def main(argv=None):
                        "erasures": erasures, "kernel": args.kernel, "nontemporal": bool(args.nt),
                        "parallelism": f"stripes round-robin over {world} GPU(s), no collective"},
             "rehearsal": rehearsal,
+            "full": full,
+            "outputs_dumped": dumped,
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_note,
                          "frac_worst_rank": min(fracs), "frac_per_rank": fracs,
@@ -1189,7 +1285,7 @@ def main(argv=None):
             **({"e2e_per_rank": e2e_per_rank, "e2e_aggregate": e2e_agg} if world > 1 else {}),
             "cpu_fallbacks": sum(p["cpu_fallbacks"] for p in per_rank),
             "cpu_calls": sum(p["cpu_calls"] for p in per_rank),
-            "selfcheck_parity_ok": ok,
+            "selfcheck_parity_ok": ok if full else None,  # not checked in a plain run
             "selfcheck_vs_reference_cpu": cpu_ok,
             "e2e_ok": e2e_ok,
             "distinct_devices_ok": devices_ok,

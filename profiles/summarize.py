@@ -1,10 +1,10 @@
-"""Summarise rocprofv3 outputs of a default bench.py run into profiles/<tag>_*.json.
+"""Summarise rocprofv3 outputs of a `bench.py --full` run into profiles/<tag>_*.json.
 
 Inputs (written on the GPU box under gpurun_out/):
   <trace>/run_kernel_stats.csv, <trace>/run_kernel_trace.csv
-      from  rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py
-  <fetch>/run_counter_collection.csv   from  rocprofv3 --pmc FETCH_SIZE -- python3 bench.py
-  <write>/run_counter_collection.csv   from  rocprofv3 --pmc WRITE_SIZE -- python3 bench.py
+      from  rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full
+  <fetch>/run_counter_collection.csv   from  rocprofv3 --pmc FETCH_SIZE -- python3 bench.py --full
+  <write>/run_counter_collection.csv   from  rocprofv3 --pmc WRITE_SIZE -- python3 bench.py --full
 
 HBM-traffic correction (MI355X_MICROARCH.md §HBM): on gfx950 FETCH_SIZE
 reports exactly half of the bytes of a wide coalesced streaming read, so the
@@ -13,7 +13,7 @@ Both counters are in KiB.  Per kernel only the full-size launches (the
 largest grid of that kernel name) are averaged, so the bench's one-stripe
 self-check launches are excluded.
 
-Kernels: every launch shape of the default bench line -- the timed C3 encode
+Kernels: every launch shape of the `--full` bench line -- the timed C3 encode
 and decode{0} (96 stripes), the configs block's other C3 decode shapes (a
 seeded single data erasure, XOR-only like decode{0} and so the same kernel:
 told apart by launch order -- the timed steps' W + K launches come first,
@@ -107,7 +107,7 @@ def main():
     a = ap.parse_args()
 
     kid = kernel_build_id()
-    out = {"workload_key": WORKLOAD_KEY, "source": "rocprofv3 (ROCm 7.2) on MI355X, `python3 bench.py` defaults",
+    out = {"workload_key": WORKLOAD_KEY, "source": "rocprofv3 (ROCm 7.2) on MI355X, `python3 bench.py --full` defaults",
            "kernel_build_id": kid, "kernels": {}}
     trace = rows(os.path.join(a.trace, "run_kernel_trace.csv"))
     fetch = rows(os.path.join(a.fetch, "run_counter_collection.csv"))

@@ -213,3 +213,25 @@ def test_e2e_aggregate_is_total_over_slowest():
     enc_only = bench.e2e_aggregate([{"data_bytes_per_pass": 2**30, "encode": {"pass_ms": 10.0, "data_GiBps": 100.0,
                                                                             "parity_ok": True}}])
     assert "decode" not in enc_only and enc_only["encode"]["data_GiBps"] == 100.0
+
+
+def test_plain_run_options():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, "")
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_indices_are_fixed_and_in_range():
+    import numpy as np
+    B, n_sh, S, n = 3, 4, 1000, 500
+    b, i, o = bench.dump_indices(B, n_sh, S, n, seed=5)
+    assert len(b) == len(i) == len(o) == n
+    assert b.min() >= 0 and b.max() < B and i.min() >= 0 and i.max() < n_sh and o.min() >= 0 and o.max() < S
+    flat = (b * n_sh + i) * S + o
+    assert np.all(np.diff(flat) >= 0)
+    again = bench.dump_indices(B, n_sh, S, n, seed=5)
+    assert all(np.array_equal(x, y) for x, y in zip((b, i, o), again))  # the same sample in every run
+    assert not np.array_equal(flat, (lambda t: (t[0] * n_sh + t[1]) * S + t[2])(bench.dump_indices(B, n_sh, S, n, 6)))

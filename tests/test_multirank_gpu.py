@@ -8,7 +8,7 @@ erasures {0,1,2,3} (C4's pattern), and the synchronous drop-in decode -- and
 the union of their results is checked against the CPU oracle on the same
 seeded stripes: every stripe coded exactly once, bytes identical.
 
-Also bench.py's own multi-rank entry point: `--gpus 2` with the one-device
+Also bench.py itself: a plain run with --dump-outputs; `--full --gpus 2` with the one-device
 rehearsal flag spawns two ranks and reports both; without it a one-GPU box
 refuses with a non-zero exit; `--config C5` runs and names C5.
 """
@@ -152,7 +152,7 @@ def test_bench_gpus2_rehearsal_spawns_two_ranks(gpu):
     # the N > 1 line is complete: rank 0's CPU baseline on
     # its stripe 0, every rank's encode / decode fractions and configs block
     # (incl. C4), the worst-rank roofline fraction beside rank 0's
-    r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--stripes", "4", "--cpu-seconds", "1"],
+    r = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--stripes", "4", "--cpu-seconds", "1"],
                {"ECGPU_BENCH_ONE_DEVICE": "1"}, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -211,7 +211,7 @@ def test_bench_gpus_beyond_visible_devices_fails(gpu):
 
 
 def test_bench_config_c5(gpu):
-    r = _bench(["--config", "C5", "--stripes", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
+    r = _bench(["--full", "--config", "C5", "--stripes", "2", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
                 "--no-configs"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -219,3 +219,48 @@ def test_bench_config_c5(gpu):
     assert (d["config"]["k"], d["config"]["m"], d["config"]["shard_bytes"]) == (12, 4, 16 << 20)
     assert d["decode_kernel"] is None and d["selfcheck_parity_ok"] is True
     assert d["e2e"]["encode"]["parity_ok"] and "decode" not in d["e2e"]  # C5 has no decode
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(gpu, tmp_path, capfd):
+    """A plain run (no --full) times the steps and prints the line with every
+    further measurement absent; --dump-outputs writes the last step's parity
+    and rebuilt shards as float32, identically for both multiply engines on the
+    same seeded inputs (so two builds compare output for output)."""
+    import bench
+    lines, dumps = {}, {}
+    for kernel in ("perm", "lds"):
+        out = tmp_path / kernel
+        capfd.readouterr()
+        rc = bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--stripes", "2", "--kernel", kernel,
+                         "--dump-outputs", str(out)])
+        assert rc == 0
+        lines[kernel] = _line(capfd.readouterr().out)
+        dumps[kernel] = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+    d = lines["perm"]
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] > 0 and d["unit"] == "GiB/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert d["metric"] == bench.HEADLINE_METRIC
+    # ms_per_step is the wall time of one timed step: value's own denominator
+    want = 3 * 2 * 2 * 10 * (4 << 20) / (d["ms_per_step"] * 3 / 1e3) / 2**30
+    # the line rounds ms_per_step to 1e-4 ms and value to 1e-3 GiB/s
+    assert abs(d["value"] - want) <= want * 1e-4 / d["ms_per_step"] + 2e-3, (d["value"], want)
+    assert len(d["per_rank"][0]["encode_launch_ms"]) == 3  # --steps sets the number of timed steps
+    for moved in ("configs", "c5_sharded", "cpu_baseline", "cpu_baseline_per_gpu_share", "cpu_baseline_all_cores",
+                  "cpu_baseline_o3", "e2e", "copy_ceiling", "xor_stream_probe", "selfcheck_parity_ok",
+                  "selfcheck_vs_reference_cpu", "e2e_ok"):
+        assert d[moved] is None, moved
+    assert d["cpu_fallbacks"] == 0 and d["cpu_calls"] == 0
+    names = ["parity_edges.npy", "parity_sample.npy", "rebuilt_edges.npy", "rebuilt_sample.npy"]
+    assert sorted(d["outputs_dumped"]) == names == sorted(dumps["perm"])
+    total = 0
+    for f in names:
+        a, b = dumps["perm"][f], dumps["lds"][f]
+        assert a.dtype == np.float32 and list(a.shape) == d["outputs_dumped"][f]
+        assert a.min() >= 0 and a.max() <= 255 and np.array_equal(a, np.floor(a))  # bytes
+        assert np.array_equal(a, b), f  # same inputs, the other engine: the same bytes
+        total += a.nbytes
+    assert total <= 64 * 10**6
+    assert dumps["perm"]["parity_edges.npy"].shape == (2, 4, 2 * bench.DUMP_EDGE_BYTES)
+    assert dumps["perm"]["rebuilt_edges.npy"].shape == (2, 1, 2 * bench.DUMP_EDGE_BYTES)
+    assert dumps["perm"]["parity_sample.npy"].shape == (bench.DUMP_SAMPLE_BYTES,)
+    assert len(np.unique(dumps["perm"]["parity_sample.npy"])) == 256  # random data: not a blank buffer

@@ -9,7 +9,7 @@ set -e
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/c4
-BCMD="python3 bench.py --cpu-seconds 0 --e2e-stripes 0"
+BCMD="python3 bench.py --full --cpu-seconds 0 --e2e-stripes 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/c4/trace -o run -- $BCMD > gpurun_out/c4/trace.log 2>&1
 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/c4/pmc_sq -o run -- $BCMD > gpurun_out/c4/pmc_sq.log 2>&1
 timeout -s KILL 300 rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_DRAM_CREDIT_STALL_sum GRBM_GUI_ACTIVE GRBM_COUNT --output-format csv -d gpurun_out/c4/pmc_tcc -o run -- $BCMD > gpurun_out/c4/pmc_tcc.log 2>&1
