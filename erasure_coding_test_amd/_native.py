@@ -117,6 +117,14 @@ SIGNATURES = {
     "ecgpu_plan_set_kernel": (c_int, [c_void_p, c_int, c_int]),
     "ecgpu_plan_launch": (c_int, [c_void_p, c_void_p]),
     "ecgpu_plan_destroy": (None, [c_void_p]),
+    "ecgpu_scrub_create": (c_void_p, [c_int, c_int, c_int, c_int_p, c_int]),
+    "ecgpu_scrub_bind": (c_int, [c_void_p, c_int, c_void_pp, c_void_pp, c_int64]),
+    "ecgpu_scrub_launch": (c_int, [c_void_p, c_void_p]),
+    "ecgpu_scrub_read": (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    "ecgpu_scrub_device_results": (c_void_p, [c_void_p]),
+    "ecgpu_scrub_engine": (c_int, [c_void_p]),
+    "ecgpu_scrub_destroy": (None, [c_void_p]),
+    "ecgpu_scrub_blame_matrix": (c_int, [c_int, c_int, c_int_p, c_int_p, c_int_p]),
     "ecgpu_recommended_shard_stride": (c_int64, [c_int64]),
     "ecgpu_recommended_shard_stride_km": (c_int64, [c_int64, c_int, c_int]),
     "ecgpu_pipeline_create": (c_void_p, [c_int, c_int, c_int_p, c_int64, c_int, c_int]),

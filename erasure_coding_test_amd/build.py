@@ -20,7 +20,8 @@ a newer mtime decides.  The library carries content IDs (ecgpu_build_id):
      dispatch_w8.hip and the defaults of the knobs it reads) + HIP flags +
      hipcc --version -- the identity a rocprofv3 PMC record of the bench's
      launches is valid for (profiles/summarize.py writes it, bench.py checks it)
-  2  the same for the w = 16 / 32 kernels, 3 for the GF(2) packet kernels.
+  2  the same for the w = 16 / 32 kernels, 3 for the GF(2) packet kernels,
+     4 for the scrub kernels.
 """
 from __future__ import annotations
 
@@ -46,11 +47,12 @@ HOST_SRCS = ["gf_host.cpp", "matrix_host.cpp", "planner.cpp", "schedule_host.cpp
 # (source, object, extra flags): the specialised kernel table is split into
 # one translation unit per output-row count so the four compile in parallel
 HIP_UNITS = [(f, f + ".o", []) for f in ("ecgpu_runtime.hip", "dispatch_w8.hip", "dispatch_wide.hip", "accum.hip",
-                                           "pipeline.hip", "packets.hip")] + [
-    (f"{t}.hip", f"{t}_r{r}.hip.o", [f"-DECGPU_SPEC_R={r}"]) for t in ("gf_spec", "wide_spec") for r in (1, 2, 3, 4)]
+                                           "pipeline.hip", "packets.hip", "scrub.hip")] + [
+    (f"{t}.hip", f"{t}_r{r}.hip.o", [f"-DECGPU_SPEC_R={r}"]) for t in ("gf_spec", "wide_spec", "scrub_spec")
+    for r in (1, 2, 3, 4)]
 HDRS = ["buffer_contract.hpp", "cpu_fallback.hpp", "cpu_exec.hpp", "gf_host.hpp", "knobs.hpp", "shard_stride.hpp", "host_sync.hpp", "matrix_host.hpp", "planner.hpp", "schedule_host.hpp", "gf_kernels.hpp", "gf_kernels_w8.hpp", "gf_kernels_wide.hpp",
         "gf_kernels_packets.hpp", "gf_spec.hpp", "wide_spec.hpp", "diag_kernels_w8.hpp",
-        "runtime.hpp"]
+        "runtime.hpp", "scrub_kernels.hpp", "scrub_spec.hpp"]
 DROPIN_SRCS = ["jerasure_dropin.cpp", "jerasure_surface.cpp"]
 
 CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", f"-I{INCLUDE}", f"-I{CSRC}"]
@@ -88,6 +90,8 @@ KERNEL_FAMILIES = {
              ["ECGPU_WIDE", "ECGPU_NIB16", "ECGPU_WIDE_UNITS", "ECGPU_WIDE_PIPE", "ECGPU_WIDE16_BPCU",
               "ECGPU_WIDE16_UNITS"]),
     "packets": (["gf_kernels_w8.hpp", "gf_kernels_packets.hpp", "packets.hip"], ["ECGPU_PACKET"]),
+    "scrub": (["gf_kernels_w8.hpp", "scrub_kernels.hpp", "scrub_spec.hip", "scrub_spec.hpp", "scrub.hip"],
+              ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_SCRUB_LATE"]),
 }
 
 
@@ -128,7 +132,7 @@ def toolchain(compiler: str) -> str:
 
 
 def build_ids() -> dict:
-    """{'build', 'kernels' (w = 8), 'wide', 'packets'}: 16-hex content IDs (see
+    """{'build', 'kernels' (w = 8), 'wide', 'packets', 'scrub'}: 16-hex content IDs (see
     the module doc and KERNEL_FAMILIES)."""
     all_srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
                       if f.endswith((".hip", ".cpp", ".hpp")) and not f.startswith("diag_kernels"))
@@ -178,7 +182,8 @@ def build_native(verbose: bool = True) -> dict:
     for src in HOST_SRCS:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src + ".o")
         extra = ([f'-DECGPU_BUILD_ID="{ids["build"]}"', f'-DECGPU_KERNEL_ID="{ids["kernels"]}"',
-                  f'-DECGPU_WIDE_ID="{ids["wide"]}"', f'-DECGPU_PACKETS_ID="{ids["packets"]}"']
+                  f'-DECGPU_WIDE_ID="{ids["wide"]}"', f'-DECGPU_PACKETS_ID="{ids["packets"]}"',
+                  f'-DECGPU_SCRUB_ID="{ids["scrub"]}"']
                  if src == "capi_host.cpp" else [])
         cmd = [CXX] + CXXFLAGS + extra + ["-fvisibility=hidden", "-c", s, "-o", o]
         if _stale(o, [s] + hdrs, cmd):

@@ -62,6 +62,7 @@ constexpr KnobDef kDefs[int(Knob::kCount)] = {
     {"ECGPU_PIPE_CONTIG", "pipe_contig", 1},
     {"ECGPU_PIPE_FLAT", "pipe_flat", 1},
     {"ECGPU_LINK_CALLS", "link_calls", 1},
+    {"ECGPU_SCRUB_LATE", "scrub_late", 1},
 };
 
 constexpr int kUnset = INT_MIN;

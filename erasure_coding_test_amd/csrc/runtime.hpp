@@ -5,6 +5,7 @@
 //   accum.hip          HBM-resident ECX parity accumulators
 //   pipeline.hip       host-memory pipelines and multi-device groups
 //   packets.hip        GF(2) bit-matrix / schedule coding
+//   scrub.hip          stripe scrub: fused parity verify with shard blame
 // Everything here lives in ecgpu::rt with hidden visibility: the shared
 // library exports only the ECGPU_API functions.
 #pragma once
@@ -133,6 +134,8 @@ void plan_free(ecgpu_plan* p);
 // launches wait for it through plan_wait_tables
 int plan_upload_tables(ecgpu_plan* p, std::vector<uint8_t>&& host);
 int plan_wait_tables(ecgpu_plan* p, hipStream_t stream);
+// the same wait on the host (what a blocking plan_bind does first)
+int plan_sync_tables(ecgpu_plan* p);
 // the width-specific halves of plan_init / plan_launch (dispatch_w8.hip,
 // dispatch_wide.hip); p->coef is sized rows x nsrc
 int plan_init_w8(ecgpu_plan* p, const int* coefs);

@@ -71,7 +71,7 @@ ECGPU_API const char* ecgpu_version(void);
 /* Content IDs of the built library (16 hex digits): what = 0 the whole
  * library, 1 the w = 8 kernels and their dispatch (the identity a rocprofv3
  * PMC record of the bench's launches is valid for), 2 the w = 16 / 32
- * kernels, 3 the GF(2) packet kernels. */
+ * kernels, 3 the GF(2) packet kernels, 4 the scrub kernels. */
 ECGPU_API const char* ecgpu_build_id(int what);
 ECGPU_API const char* ecgpu_last_error(void);         /* thread-local message */
 /* Tuning / A-B switches (knobs.hpp lists them: the residency cap, engines,
@@ -260,6 +260,81 @@ ECGPU_API int ecgpu_plan_check_buffers(int rows, int nsrc, int stripes, const ui
 ECGPU_API int ecgpu_plan_set_kernel(ecgpu_plan* p, int kind, int nontemporal);
 ECGPU_API int ecgpu_plan_launch(ecgpu_plan* p, void* stream);
 ECGPU_API void ecgpu_plan_destroy(ecgpu_plan* p);
+
+/* ------------------------- stripe scrub: fused parity verify with blame -- */
+/* Is each stripe still a codeword of the m x k coding matrix, and if not,
+ * which shard is wrong?  One fused pass reads the k + m shards of every
+ * stripe once, compares the recomputed parity with the stored one in
+ * registers and writes nothing for a clean stripe (no scratch parity, the
+ * encode launch's bytes, all of them reads).  Plan-style: create (matrix
+ * tables uploaded once), bind (blocking; tables of device pointers, stripe-
+ * major like ecgpu_encode_batch), launch (asynchronous on a hipStream_t,
+ * graph-capturable once bound, stripes batched), read.
+ *
+ * For stripe s, byte offset x and coding row i the syndrome is
+ *     syn[i][x] = coding[s][i][x] ^ XOR_j matrix[i][j] * data[s][j][x]   (GF(2^8));
+ * x is bad when any syn[i][x] != 0.  `blame` is the set of shards that ALONE
+ * explain every bad position of the stripe: at a bad position data shard j is
+ * a candidate iff some e gives syn[i] == matrix[i][j] * e for all i, coding
+ * shard p iff syn[i] == 0 for all i != p; blame is the AND over the stripe's
+ * bad positions.  (The data-shard test runs without a division: with pivot
+ * row p_j, the first row where column j is non-zero, and ratios D[i][j] =
+ * matrix[i][j] / matrix[p_j][j], shard j is a candidate iff syn[i] ==
+ * D[i][j] * syn[p_j] for all i; an all-zero column is never a candidate.
+ * ecgpu_scrub_blame_matrix returns both.)  Consequences:
+ *   - with an MDS matrix and m >= 2, a stripe damaged in one shard has
+ *     exactly that shard's bit set: hand it to ecgpu_decode_plan as the
+ *     erasure list;
+ *   - with m == 1 every shard is a candidate (k + 1 bits);
+ *   - damage in two or more shards usually gives 0, but it can mimic a third
+ *     shard -- RS corrects only floor(m / 2) unknown errors -- so a caller
+ *     confirms a repair by scrubbing again;
+ *   - a non-MDS matrix can give several bits: k = m = 2, matrix {1,1, 1,0}:
+ *     damage in data shard 1 cannot be told from damage in coding shard 0,
+ *     blame == 0b0110.
+ * Shard ids are those of ecgpu_decode_plan: data 0..k-1, coding k..k+m-1.
+ *
+ * Buffers: device pointers only, like ecgpu_plan_bind.  The pointer tables
+ * are uploaded below the buffer contract of ecgpu_plan_check_buffers: scrub
+ * writes no shard byte, so shards may overlap or repeat.  Shapes with
+ * k <= 16 and m <= 4 whose pointers are all 16-B aligned run the specialised
+ * 16-B-column kernel (and a byte kernel for the tail size % 16); every other
+ * shape or alignment runs the byte kernel alone (ecgpu_scrub_engine).
+ *
+ * Out of scope: w = 16 / 32; the GF(2) packet codes; host-memory shards and
+ * the CPU executor (a scrub never runs on the CPU: ecgpu_cpu_call_count and
+ * ecgpu_fallback_count do not move); the drop-in libjerasure_amd.so, since
+ * the reference has no such function. */
+#define ECGPU_SCRUB_MAX_M 8
+typedef struct ecgpu_scrub_result {
+  uint64_t bad_bytes[ECGPU_SCRUB_MAX_M]; /* row i: positions with syn[i][x] != 0                      */
+  uint64_t bad_cols;                     /* bad positions                                             */
+  uint64_t first_bad;                    /* lowest bad position; UINT64_MAX when clean                */
+  uint64_t blame;                        /* bit = shard id 0..k+m-1; 0 when clean                     */
+} ecgpu_scrub_result;                    /* 88 bytes */
+typedef struct ecgpu_scrub ecgpu_scrub;
+/* NULL (ecgpu_last_error) unless w == 8, k >= 1, 1 <= m <= ECGPU_SCRUB_MAX_M,
+ * k + m <= 64 and matrix (m x k, row-major) is not NULL -- checked before any
+ * HIP call.  device < 0: the current device. */
+ECGPU_API ecgpu_scrub* ecgpu_scrub_create(int k, int m, int w, const int* matrix, int device);
+ECGPU_API int ecgpu_scrub_bind(ecgpu_scrub* s, int stripes, const uint8_t* const* data /* [s*k+j] */,
+                               const uint8_t* const* coding /* [s*m+i] */, int64_t size);
+/* Asynchronous: resets the results, verifies, computes the blame of the bad
+ * stripes -- all kernels, so a captured launch replays correctly. */
+ECGPU_API int ecgpu_scrub_launch(ecgpu_scrub* s, void* stream);
+/* Synchronises `stream`, copies the first min(cap, stripes) results to out
+ * and sets blame = 0 where bad_cols == 0; returns how many (< 0: error). */
+ECGPU_API int ecgpu_scrub_read(ecgpu_scrub* s, void* stream, ecgpu_scrub_result* out, int cap);
+/* The raw results in device memory (valid until the next bind that grows
+ * them): blame is meaningful only where bad_cols > 0. */
+ECGPU_API const ecgpu_scrub_result* ecgpu_scrub_device_results(ecgpu_scrub* s);
+/* 0: the specialised vector kernel runs for the current binding (before a
+ * bind: for the shape), 1: the byte kernel only. */
+ECGPU_API int ecgpu_scrub_engine(ecgpu_scrub* s);
+ECGPU_API void ecgpu_scrub_destroy(ecgpu_scrub* s);
+/* Host only: pivots[k] (-1 for an all-zero column) and ratios[m*k] of the
+ * blame test above. */
+ECGPU_API int ecgpu_scrub_blame_matrix(int k, int m, const int* matrix, int* pivots, int* ratios);
 
 /* ECX-style incremental parity accumulation (ecx_datanode_main.cpp:680-735)
  * with the m accumulators resident in HBM.  Source blocks arrive one at a
