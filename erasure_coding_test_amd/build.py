@@ -46,7 +46,8 @@ HOST_SRCS = ["gf_host.cpp", "matrix_host.cpp", "planner.cpp", "schedule_host.cpp
              "cpu_fallback.cpp", "cpu_exec.cpp"]
 # (source, object, extra flags): the specialised kernel table is split into
 # one translation unit per output-row count so the four compile in parallel
-HIP_UNITS = [(f, f + ".o", []) for f in ("ecgpu_runtime.hip", "dispatch_w8.hip", "dispatch_wide.hip", "accum.hip",
+HIP_UNITS = [(f, f + ".o", []) for f in ("ecgpu_runtime.hip", "plans.hip", "devices.hip", "contexts.hip",
+                                           "host_memory.hip", "dispatch_w8.hip", "dispatch_wide.hip", "accum.hip",
                                            "pipeline.hip", "packets.hip", "scrub.hip")] + [
     (f"{t}.hip", f"{t}_r{r}.hip.o", [f"-DECGPU_SPEC_R={r}"]) for t in ("gf_spec", "wide_spec", "scrub_spec")
     for r in (1, 2, 3, 4)]
@@ -81,8 +82,9 @@ def _run_parallel(cmds):
 # policy), plus the default values of the knobs that dispatch reads -- so a
 # w = 32 or packet edit leaves the w = 8 ID, which the bench's PMC traffic
 # records are keyed to, unchanged.  The synchronous calls' staging
-# (ecgpu_runtime.hip) and the measurement-only kernels (diag_kernels*) are in
-# no family.
+# (ecgpu_runtime.hip), the units under it (plans.hip, devices.hip,
+# contexts.hip, host_memory.hip) and the measurement-only kernels
+# (diag_kernels*) are in no family.
 KERNEL_FAMILIES = {
     "kernels": (["gf_kernels_w8.hpp", "gf_spec.hip", "gf_spec.hpp", "dispatch_w8.hip"],
                 ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_KERNEL", "ECGPU_NT"]),

@@ -1,9 +1,11 @@
-// ecgpu_runtime.hip -- device side of include/ecgpu.h: plans, contexts,
-// staging of host buffers, the synchronous calls with their failure contract,
-// and the hot-path C ABI.  How a plan launches is dispatch_w8.hip (w = 8) and
-// dispatch_wide.hip (w = 16 / 32).  The ECX accumulators (accum.hip), host
-// pipelines (pipeline.hip) and GF(2) packet coding (packets.hip) build on the
-// helpers this file exports to them through runtime.hpp.
+// ecgpu_runtime.hip -- the synchronous calls of include/ecgpu.h: how a call's
+// host buffers are staged, the three execution modes, the failure contract,
+// split calls, the link rule, and the jerasure / galois / reed_sol C ABI.
+// What they build on lives in plans.hip (the plan lifecycle and its ABI),
+// devices.hip (HIP error classification and device selection), contexts.hip
+// (the context pool and its staging buffers) and host_memory.hip (where a
+// buffer lives, shard copies); how a plan launches is dispatch_w8.hip (w = 8)
+// and dispatch_wide.hip (w = 16 / 32).
 //
 // Execution model (MI355X-first, not the reference's byte loops):
 //   * every hot-path call is planned on the host into ONE fused
@@ -20,17 +22,11 @@
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
+#include <cstdint>
 #include <cstring>
-#include <deque>
-#include <functional>
-#include <list>
-#include <map>
-#include <memory>
 #include <mutex>
 #include <string>
+#include <system_error>
 #include <thread>
 #include <utility>
 #include <vector>
@@ -41,388 +37,14 @@
 #include "gf_host.hpp"
 #include "gf_kernels.hpp"
 #include "gf_spec.hpp"
-#include "host_sync.hpp"
 #include "knobs.hpp"
-#include "matrix_host.hpp"
 #include "planner.hpp"
 #include "runtime.hpp"
 
 using namespace ecgpu;
 using namespace ecgpu::rt;
-using dev::ApplyArgs;
-using dev::u32x4;
 
 ECGPU_RT_BEGIN
-
-// t_err / fail / ecgpu_last_error live in capi_host.cpp (host code, so the
-// host-only checks -- buffer contract, knobs -- report through them too)
-
-// Errors after which the device's context is unusable for the rest of the
-// process (a kernel fault, a lost / missing device or driver): the device is
-// marked lost, and with ECGPU_CPU_FALLBACK later synchronous calls on it go
-// straight to the CPU (cpu_fallback.hpp).  hipErrorInvalidDevice is not one:
-// a bad ordinal argument returns it (ecgpu_device_pci_bus_id(99)) on a
-// healthy device.
-bool sticky(hipError_t e) {
-  switch (e) {
-    case hipErrorNotInitialized:
-    case hipErrorDeinitialized:
-    case hipErrorInsufficientDriver:
-    case hipErrorNoDevice:
-    case hipErrorNoBinaryForGpu:
-    case hipErrorECCNotCorrectable:
-    case hipErrorIllegalAddress:
-    case hipErrorLaunchTimeOut:
-    case hipErrorContextIsDestroyed:
-    case hipErrorAssert:
-    case hipErrorLaunchFailure:
-      return true;
-    default:
-      return false;
-  }
-}
-
-// The device the current synchronous call targets (CallDeviceScope), -1
-// outside one.
-thread_local int t_call_device = -1;
-
-CallDeviceScope::CallDeviceScope(int device) : prev(t_call_device) { t_call_device = device; }
-CallDeviceScope::~CallDeviceScope() { t_call_device = prev; }
-
-int fail_hip(hipError_t e, const char* what) {
-  std::string msg = std::string(what) + ": " + hipGetErrorString(e);
-  int d = t_call_device;
-  if (d < 0 && hipGetDevice(&d) != hipSuccess) d = -1;
-  bool lost = sticky(e);
-  if (!lost && e == hipErrorUnknown && d >= 0) {
-    // ordinary failures return it too: sticky only when the device still
-    // fails a synchronize afterwards
-    DeviceGuard g(d);
-    (void)hipGetLastError();
-    lost = hipDeviceSynchronize() != hipSuccess;
-    (void)hipGetLastError();
-  }
-  if (lost && d >= 0) mark_device_lost(d);
-  // The library reports the error through its own channel; HIP's per-thread
-  // last error is shared with the caller's HIP code in the same process, so
-  // a handled failure (a bad ordinal, an OOM the CPU completed) must not
-  // surface in the caller's next error check (torch's launch checks did).
-  (void)hipGetLastError();
-  return fail(ECGPU_ERR_HIP, msg);
-}
-
-
-// One non-blocking stream per device for coefficient-table uploads: a plan's
-// creation does not wait for its tables (one blocking copy cost ~12 us,
-// tools/hip_overheads.cpp); its launches wait on the upload's event instead.
-hipStream_t upload_stream(int device) {
-  static hostsync::PerDevice<hipStream_t> streams;
-  return streams.get(device, [](int dev) {
-    DeviceGuard g(dev);
-    hipStream_t s = nullptr;
-    return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? s : nullptr;
-  });
-}
-
-// Allocates p->d_tabs and uploads `host` into it without waiting (the plan
-// keeps `host` alive until the upload has completed).
-int plan_upload_tables(ecgpu_plan* p, std::vector<uint8_t>&& host) {
-  DeviceGuard g(p->device);
-  ECGPU_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_tabs), host.size()));
-  p->host_tabs = std::move(host);
-  const hipStream_t s = upload_stream(p->device);
-  if (!s) {  // no stream: a blocking copy
-    ECGPU_HIP(hipMemcpy(p->d_tabs, p->host_tabs.data(), p->host_tabs.size(), hipMemcpyHostToDevice));
-    return ECGPU_OK;
-  }
-  ECGPU_HIP(hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming));
-  ECGPU_HIP(hipMemcpyAsync(p->d_tabs, p->host_tabs.data(), p->host_tabs.size(), hipMemcpyHostToDevice, s));
-  ECGPU_HIP(hipEventRecord(p->uploaded, s));
-  p->upload_pending = true;
-  return ECGPU_OK;
-}
-
-// Waits for the plan's table upload on the host (a no-op once it completed).
-int plan_sync_tables(ecgpu_plan* p) {
-  if (!p->upload_pending) return ECGPU_OK;
-  ECGPU_HIP(hipEventSynchronize(p->uploaded));
-  p->upload_pending = false;
-  std::vector<uint8_t>().swap(p->host_tabs);
-  return ECGPU_OK;
-}
-
-// Orders `stream` after the plan's table upload (a no-op once it completed).
-// A blocking bind has already waited for it, so a bound plan launches inside
-// a stream capture without touching the event; a plan bound on a stream
-// (the synchronous calls) may not be captured before its upload completed.
-int plan_wait_tables(ecgpu_plan* p, hipStream_t stream) {
-  if (!p->upload_pending) return ECGPU_OK;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
-    return fail(ECGPU_ERR, "plan tables still uploading: bind the plan without a stream before capturing it");
-  (void)hipGetLastError();
-  const hipError_t q = hipEventQuery(p->uploaded);
-  if (q == hipSuccess) {
-    p->upload_pending = false;
-    std::vector<uint8_t>().swap(p->host_tabs);
-    return ECGPU_OK;
-  }
-  if (q != hipErrorNotReady) return fail_hip(q, "table upload");
-  (void)hipGetLastError();  // not ready is not an error
-  ECGPU_HIP(hipStreamWaitEvent(stream, p->uploaded, 0));
-  return ECGPU_OK;
-}
-
-void plan_free(ecgpu_plan* p) {
-  if (!p) return;
-  DeviceGuard g(p->device);
-  if (p->uploaded) {
-    (void)hipEventSynchronize(p->uploaded);  // the table upload may still read host_tabs
-    (void)hipEventDestroy(p->uploaded);
-  }
-  if (p->d_tabs) (void)hipFree(p->d_tabs);
-  if (p->d_ptrs) (void)hipFree(p->d_ptrs);
-  delete p;
-}
-
-int plan_init(ecgpu_plan* p, int rows, int nsrc, const int* coefs, int device, int w) {
-  p->device = device;
-  p->rows = rows;
-  p->nsrc = nsrc;
-  p->w = w;
-  p->kind = knob(Knob::kKernel);
-  p->nt = std::min(kStorePolicies - 1, std::max(0, knob(Knob::kNt)));
-  const size_t n = size_t(rows) * nsrc;
-  p->coef.resize(n);
-  if (w != 8) return plan_init_wide(p, coefs);
-  return plan_init_w8(p, coefs);
-}
-
-// With a stream the pointer tables are uploaded asynchronously on it; unless
-// `keep_alive` (the caller keeps src/dst alive until it synchronises the
-// stream, as execute() does) the call waits for the upload.
-int plan_bind(ecgpu_plan* p, int stripes, const uint8_t* const* src, uint8_t* const* dst, int64_t size,
-              hipStream_t stream, bool keep_alive) {
-  const size_t ns = size_t(stripes) * p->nsrc, nd = size_t(stripes) * p->rows;
-  DeviceGuard g(p->device);
-  // a blocking bind settles the table upload too (it overlapped the table
-  // build-up to here); a bind on a stream leaves it to the launch
-  if (!stream)
-    if (int rc = plan_sync_tables(p)) return rc;
-  if (ns + nd > p->cap_ptrs) {
-    if (p->d_ptrs) ECGPU_HIP(hipFree(p->d_ptrs));
-    p->d_ptrs = nullptr;
-    p->cap_ptrs = 0;
-    ECGPU_HIP(hipMalloc(reinterpret_cast<void**>(&p->d_ptrs), (ns + nd) * sizeof(void*)));
-    p->cap_ptrs = ns + nd;
-  }
-  p->d_src = static_cast<const uint8_t**>(static_cast<void*>(p->d_ptrs));
-  p->d_dst = static_cast<uint8_t**>(static_cast<void*>(p->d_ptrs + ns));
-  bool aligned = true;
-  for (size_t i = 0; i < ns; ++i) aligned &= (reinterpret_cast<uintptr_t>(src[i]) & 15u) == 0;
-  for (size_t i = 0; i < nd; ++i) aligned &= (reinterpret_cast<uintptr_t>(dst[i]) & 15u) == 0;
-  if (stream && keep_alive) {
-    // the caller's arrays outlive the stream sync: no wait here
-    ECGPU_HIP(hipMemcpyAsync(p->d_src, src, ns * sizeof(void*), hipMemcpyHostToDevice, stream));
-    ECGPU_HIP(hipMemcpyAsync(p->d_dst, dst, nd * sizeof(void*), hipMemcpyHostToDevice, stream));
-  } else {
-    // one upload of [sources | destinations]
-    std::vector<const void*> host(ns + nd);
-    std::memcpy(host.data(), src, ns * sizeof(void*));
-    std::memcpy(host.data() + ns, dst, nd * sizeof(void*));
-    if (stream) {
-      ECGPU_HIP(hipMemcpyAsync(p->d_ptrs, host.data(), (ns + nd) * sizeof(void*), hipMemcpyHostToDevice, stream));
-      ECGPU_HIP(hipStreamSynchronize(stream));  // the host table dies on return
-    } else {
-      ECGPU_HIP(hipMemcpy(p->d_ptrs, host.data(), (ns + nd) * sizeof(void*), hipMemcpyHostToDevice));
-    }
-  }
-  p->stripes = stripes;
-  p->size = size;
-  p->aligned = aligned;
-  return ECGPU_OK;
-}
-
-// ------------------------------------------------------ context pool ----
-
-hostsync::IdlePool<Ctx> g_pool;  // idle contexts (process lifetime)
-
-int visible_devices();
-
-// A forced ECGPU_DEVICE that names a visible device (or any, when HIP cannot
-// tell), else -1: a device this process cannot see is ignored, with one
-// stderr line, instead of failing every call (or sending it to the CPU).
-int forced_device() {
-  const int forced = knob(Knob::kDevice);
-  if (forced < 0) return -1;
-  static const int visible = visible_devices();
-  if (visible <= 0 || forced < visible) return forced;
-  static std::once_flag once;
-  std::call_once(once, [&] {
-    std::fprintf(stderr, "libecgpu: ECGPU_DEVICE=%d ignored (%d visible)\n", forced, visible);
-  });
-  return -1;
-}
-
-int current_device() {
-  const int forced = forced_device();
-  if (forced >= 0) return forced;
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess) d = 0;
-  return d;
-}
-
-// ECGPU_DEVICES (or ecgpu_set_devices): the devices the synchronous
-// host-memory calls spread over.  Each calling thread is given one of them,
-// round-robin in the order threads make their first such call, and keeps it
-// -- so the reference client's byte-range encode pthreads
-// (client_main.cpp:1074-1164) each drive their own GPU and PCIe link.  Unset
-// (the default): the caller's current device, as before.  "all" = every
-// visible device; otherwise a comma-separated list (repeats allowed).
-std::mutex g_devices_mu;
-std::shared_ptr<const std::vector<int>> g_devices;  // null: unset
-std::atomic<uint64_t> g_device_rr{0};
-
-std::vector<int> parse_devices(const char* s, int visible) {
-  std::vector<int> out;
-  if (!s || !*s) return out;
-  if (std::strcmp(s, "all") == 0) {
-    for (int d = 0; d < visible; ++d) out.push_back(d);
-    return out;
-  }
-  const char* q = s;
-  while (*q) {
-    char* end = nullptr;
-    const long v = std::strtol(q, &end, 10);
-    if (end == q || v < 0 || v > 1023) return {};  // malformed: ignored as a whole
-    out.push_back(int(v));
-    q = end;
-    if (*q == ',') ++q;
-    else if (*q) return {};
-  }
-  return out;
-}
-
-// Visible devices, or 0 when HIP cannot tell (no GPU: lists are not checked).
-int visible_devices() {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n < 0) {
-    (void)hipGetLastError();
-    n = 0;
-  }
-  return n;
-}
-
-// The first entry of `list` that is not a visible device, or -1.
-int invisible_entry(const std::vector<int>& list, int visible) {
-  for (int d : list)
-    if (visible > 0 && d >= visible) return d;
-  return -1;
-}
-
-std::shared_ptr<const std::vector<int>> device_list() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const char* e = std::getenv("ECGPU_DEVICES");
-    if (!e || !*e) return;
-    const int n = visible_devices();
-    auto v = std::make_shared<const std::vector<int>>(parse_devices(e, n));
-    // a malformed list, or one naming a device this process cannot see, is
-    // ignored as a whole (every call would otherwise fail or fall back)
-    const int bad = invisible_entry(*v, n);
-    if (v->empty() || bad >= 0) {
-      std::fprintf(stderr, "libecgpu: ECGPU_DEVICES=\"%s\" ignored (%s)\n", e,
-                   bad >= 0 ? ("device " + std::to_string(bad) + " is not visible; " + std::to_string(n) +
-                               " visible").c_str()
-                            : "expected \"all\" or a comma-separated list of device ordinals");
-      return;
-    }
-    std::lock_guard<std::mutex> lk(g_devices_mu);
-    if (!g_devices) g_devices = v;
-  });
-  std::lock_guard<std::mutex> lk(g_devices_mu);
-  return g_devices;
-}
-
-// The device a synchronous call on host memory runs on: a forced
-// ECGPU_DEVICE, else this thread's device from the ECGPU_DEVICES list, else
-// the caller's current device.
-int host_call_device() {
-  if (const int forced = forced_device(); forced >= 0) return forced;
-  const auto list = device_list();
-  if (!list || list->empty()) return current_device();
-  thread_local std::shared_ptr<const std::vector<int>> t_list;
-  thread_local int t_dev = -1;
-  if (t_list != list) {
-    t_list = list;
-    t_dev = (*list)[size_t(g_device_rr.fetch_add(1, std::memory_order_relaxed) % list->size())];
-  }
-  return t_dev;
-}
-
-// A call naming device memory runs where that memory is (the current device,
-// as before: classify() rejects another device's buffers); an all-host call
-// takes host_call_device().
-int call_device(const std::vector<void*>& a, const std::vector<void*>& b) {
-  if (const int forced = forced_device(); forced >= 0) return forced;
-  const auto list = device_list();
-  if (!list || list->empty()) return current_device();
-  if (!all_host(a) || !all_host(b)) return current_device();
-  return host_call_device();
-}
-
-Ctx* acquire_ctx(int device, int* rc) {
-  if (Ctx* c = g_pool.acquire(device)) {
-    *rc = ECGPU_OK;
-    return c;
-  }
-  auto* c = new Ctx();
-  c->device = device;
-  DeviceGuard g(device);
-  // A blocking stream: a synchronous call on device buffers is ordered after
-  // work the caller queued on the null stream (PyTorch's default stream,
-  // e.g. the fill of a freshly allocated output), and that stream's later
-  // work after the call.  Calls from different threads still run on
-  // different contexts, unordered against each other.
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamDefault);
-  if (e != hipSuccess) {
-    *rc = fail_hip(e, "hipStreamCreateWithFlags");
-    delete c;
-    return nullptr;
-  }
-  *rc = ECGPU_OK;
-  return c;
-}
-
-void release_ctx(Ctx* c) { g_pool.release(c->device, c); }
-
-
-int ctx_plan(Ctx* c, int rows, int nsrc, const std::vector<uint32_t>& coef, int w, ecgpu_plan** out) {
-  // the engine and store policy are part of the key: a knob switched between
-  // calls (an in-process A/B) must reach the next launch (plan_init reads them)
-  const int kind = knob(Knob::kKernel), nt = std::min(kStorePolicies - 1, std::max(0, knob(Knob::kNt)));
-  PlanKey key{rows, nsrc, w, kind, nt, coef};
-  for (auto it = c->plans.begin(); it != c->plans.end(); ++it)
-    if (it->first == key) {
-      c->plans.splice(c->plans.begin(), c->plans, it);
-      *out = it->second;
-      return ECGPU_OK;
-    }
-  auto* p = new ecgpu_plan();
-  std::vector<int> ci(coef.begin(), coef.end());
-  int rc = plan_init(p, rows, nsrc, ci.data(), c->device, w);
-  if (rc != ECGPU_OK) {
-    plan_free(p);
-    return rc;
-  }
-  c->plans.emplace_front(std::move(key), p);
-  if (c->plans.size() > 64) {
-    plan_free(c->plans.back().second);
-    c->plans.pop_back();
-  }
-  *out = p;
-  return ECGPU_OK;
-}
 
 // How a synchronous call moves host (pageable or pinned) buffers, by the
 // bytes it stages (measured on MI355X, tools/hip_overheads.cpp,
@@ -458,97 +80,6 @@ bool zero_copy_pinned() { return knob(Knob::kZcPinned) != 0; }
 
 bool inline_enabled() { return knob(Knob::kInline) != 0; }
 
-int ensure_bounce(Ctx* c, size_t bytes) {
-  if (bytes <= c->bounce_cap) return ECGPU_OK;
-  DeviceGuard g(c->device);
-  if (c->bounce) ECGPU_HIP(hipHostFree(c->bounce));
-  c->bounce = nullptr;
-  c->bounce_cap = 0;
-  ECGPU_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->bounce), bytes, hipHostMallocDefault));
-  c->bounce_cap = bytes;
-  return ECGPU_OK;
-}
-
-// Coherent (fine-grained) pinned memory: the GPU does not cache it, so CPU
-// writes before a launch and GPU writes before its completion are visible to
-// the other side without cache maintenance.  Grows geometrically.
-int ensure_zc(Ctx* c, size_t bytes) {
-  if (bytes <= c->zc_cap) return ECGPU_OK;
-  DeviceGuard g(c->device);
-  if (c->zc) ECGPU_HIP(hipHostFree(c->zc));
-  c->zc = nullptr;
-  c->zc_cap = 0;
-  const size_t want = std::max(bytes, size_t(256) << 10);
-  ECGPU_HIP(hipHostMalloc(reinterpret_cast<void**>(&c->zc), want, hipHostMallocMapped | hipHostMallocCoherent));
-  c->zc_cap = want;
-  return ECGPU_OK;
-}
-
-int ensure_stage(Ctx* c, size_t bytes) {
-  if (bytes <= c->stage_cap) return ECGPU_OK;
-  DeviceGuard g(c->device);
-  if (c->stage) ECGPU_HIP(hipFree(c->stage));
-  c->stage = nullptr;
-  c->stage_cap = 0;
-  ECGPU_HIP(hipMalloc(reinterpret_cast<void**>(&c->stage), bytes));
-  c->stage_cap = bytes;
-  return ECGPU_OK;
-}
-
-// Is p device memory of `device` (usable in place)?  Host memory (pageable or
-// pinned) is staged; device memory of another GPU is rejected.
-int classify(const void* p, int device, bool* on_device) {
-  hipPointerAttribute_t attr;
-  hipError_t e = hipPointerGetAttributes(&attr, p);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *on_device = false;
-    return ECGPU_OK;
-  }
-  if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) {
-    if (attr.device != device)
-      return fail(ECGPU_ERR_ARG, "buffer lives on device " + std::to_string(attr.device) + ", call runs on " +
-                                     std::to_string(device));
-    *on_device = true;
-    return ECGPU_OK;
-  }
-  *on_device = false;
-  return ECGPU_OK;
-}
-
-// Host memory the GPU addresses in place -- hipHostMalloc'd, or registered
-// with hipHostRegister -- when [p, p + bytes) lies inside ONE such
-// allocation (HIP's range attributes; a range that leaves it would fault).
-// *dev = the device address of p.
-bool host_mapped(const void* p, size_t bytes, void** dev) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (attr.type != hipMemoryTypeHost) return false;
-  void* start = nullptr;
-  size_t range = 0;
-  if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, hipDeviceptr_t(p)) != hipSuccess ||
-      hipPointerGetAttribute(&range, HIP_POINTER_ATTRIBUTE_RANGE_SIZE, hipDeviceptr_t(p)) != hipSuccess ||
-      hipHostGetDevicePointer(dev, const_cast<void*>(p), 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  const char* c = static_cast<const char*>(p);
-  const char* s0 = static_cast<const char*>(start);
-  return c >= s0 && bytes <= range && size_t(c - s0) <= range - bytes;
-}
-
-bool is_pinned(const void* p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeHost;
-}
-
 // ------------------------------------------------------ stats counters ----
 std::mutex g_stats_mu;
 double g_stats[3] = {0, 0, 0};  // xor, gf, memcpy -- jerasure.cpp:1145-1147 order
@@ -558,60 +89,6 @@ void add_stats(const FusedOp& op) {
   g_stats[0] += op.xor_bytes;
   g_stats[1] += op.gf_bytes;
   g_stats[2] += op.memcpy_bytes;
-}
-
-// Moves n shards of `bytes` between host pointers hp[i] and device shards
-// d0 + i * dstride.  Every run of >= 2 evenly spaced host shards (a stripe
-// laid out in one host slab, as the reference client's stripe buffer is,
-// client_main.cpp:1619-1647) goes as ONE 2-D copy, the rest one copy per
-// shard.  ECGPU_PIPE_2D=0 always copies per shard.  Used by the pipelines and
-// by synchronous calls on large host buffers.
-int copy_shards(bool h2d, uint8_t* d0, size_t dstride, const std::vector<char*>& hp, size_t bytes, hipStream_t s) {
-  const bool two_d = knob(Knob::kPipe2d) != 0;
-  const size_t n = hp.size();
-  for (size_t a = 0; a < n;) {
-    size_t b = a + 1;  // [a, b): maximal run with one pitch >= bytes
-    const ptrdiff_t pitch = b < n ? hp[b] - hp[a] : 0;
-    // pageable memory only when the run is contiguous (pitch == bytes): a
-    // pageable 2-D copy with gaps between rows ran 15x slower than per-shard
-    // copies (RS(6,3) 1 MiB, shards malloc'd one by one, 16 B apart)
-    bool ok = two_d && pitch > 0 && size_t(pitch) >= bytes;
-    if (ok && size_t(pitch) != bytes) ok = is_pinned(hp[a]);  // pinned or registered
-    if (ok)
-      while (b < n && hp[b] - hp[b - 1] == pitch) ++b;
-    // a gapped run must be pinned at both ends (one registration or
-    // allocation spans it; HIP rejects a span across separately registered
-    // buffers at enqueue, which falls back below)
-    if (b - a >= 2 && size_t(pitch) != bytes && !is_pinned(hp[b - 1] + bytes - 1)) b = a + 1;
-    uint8_t* d = d0 + a * dstride;
-    if (b - a >= 2) {
-      // contiguous on both sides: one 1-D copy.  HIP's 2-D copies lost 40 % of
-      // the link when two processes shared the GPU in some allocation states
-      // (bench.py's N = 2 rehearsal after its C5 leg: 27 vs 44 GiB/s; 1-D
-      // copies 41)
-      // (ECGPU_PIPE_FLAT=0 keeps flat runs on hipMemcpy2DAsync too: an A/B switch)
-      const bool flat = size_t(pitch) == bytes && dstride == bytes && knob(Knob::kPipeFlat) != 0;
-      const hipError_t e =
-          flat ? (h2d ? hipMemcpyAsync(d, hp[a], bytes * (b - a), hipMemcpyHostToDevice, s)
-                      : hipMemcpyAsync(hp[a], d, bytes * (b - a), hipMemcpyDeviceToHost, s))
-          : h2d ? hipMemcpy2DAsync(d, dstride, hp[a], size_t(pitch), bytes, b - a, hipMemcpyHostToDevice, s)
-                : hipMemcpy2DAsync(hp[a], size_t(pitch), d, dstride, bytes, b - a, hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) {
-        a = b;
-        continue;
-      }
-      // not enqueued: fall back to one copy per shard (the error is not sticky)
-      (void)hipGetLastError();
-    }
-    for (size_t i = a; i < b; ++i) {
-      if (h2d)
-        ECGPU_HIP(hipMemcpyAsync(d0 + i * dstride, hp[i], bytes, hipMemcpyDefault, s));
-      else
-        ECGPU_HIP(hipMemcpyAsync(hp[i], d0 + i * dstride, bytes, hipMemcpyDefault, s));
-    }
-    a = b;
-  }
-  return ECGPU_OK;
 }
 
 // P3 tables of one coefficient (see build_tables).
@@ -974,26 +451,6 @@ int execute_on_gpu(const FusedOp& op, int64_t size, int device) {
   return rc;
 }
 
-Where where(const void* p) {
-  hipPointerAttribute_t attr;
-  const hipError_t e = hipPointerGetAttributes(&attr, p);
-  if (e == hipSuccess)
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged ? Where::kDevice : Where::kHost;
-  (void)hipGetLastError();
-  // unregistered pageable memory, or no GPU runtime at all (then no device
-  // memory can exist); any other failure proves nothing
-  return e == hipErrorInvalidValue || e == hipErrorNoDevice || e == hipErrorInsufficientDriver ? Where::kHost
-                                                                                                : Where::kUnknown;
-}
-
-bool all_host(const std::vector<void*>& bufs) {
-  for (void* p : bufs)
-    if (where(p) != Where::kHost) return false;
-  return true;
-}
-
-bool all_host(const FusedOp& op) { return all_host(op.srcs) && all_host(op.dsts); }
-
 // execute_on_gpu under SURVEY §8b's failure contract (cpu_fallback.hpp): a
 // HIP error on a call whose buffers are all host memory, before it wrote a
 // source (an output that is also one), completes on the CPU
@@ -1171,105 +628,6 @@ int execute(const FusedOp& op, int64_t size, const char* call) {
 ECGPU_RT_END
 // ================================================================ C ABI ====
 extern "C" {
-
-
-ECGPU_API ecgpu_plan* ecgpu_plan_create(int rows, int nsrc, const int* coefs, int device) {
-  if (rows <= 0 || nsrc <= 0 || !coefs) {
-    fail(ECGPU_ERR_ARG, "ecgpu_plan_create: rows, nsrc > 0 and coefs required");
-    return nullptr;
-  }
-  if (device < 0) device = current_device();
-  auto* p = new ecgpu_plan();
-  if (plan_init(p, rows, nsrc, coefs, device) != ECGPU_OK) {
-    plan_free(p);
-    return nullptr;
-  }
-  return p;
-}
-
-ECGPU_API int ecgpu_plan_bind(ecgpu_plan* p, int stripes, const uint8_t* const* src_ptrs, uint8_t* const* dst_ptrs,
-                              int64_t size) {
-  if (!p || stripes < 0 || size < 0 || (stripes && (!src_ptrs || !dst_ptrs)))
-    return fail(ECGPU_ERR_ARG, "ecgpu_plan_bind: bad arguments");
-  if (int rc = ecgpu_plan_check_buffers(p->rows, p->nsrc, stripes, src_ptrs, dst_ptrs, size)) return rc;
-  return plan_bind(p, stripes, src_ptrs, dst_ptrs, size, nullptr);
-}
-
-ECGPU_API int ecgpu_plan_set_kernel(ecgpu_plan* p, int kind, int nontemporal) {
-  if (!p || (kind != ECGPU_KERNEL_PERM && kind != ECGPU_KERNEL_LDS))
-    return fail(ECGPU_ERR_ARG, "ecgpu_plan_set_kernel: bad arguments");
-  p->kind = kind;
-  p->nt = std::min(kStorePolicies - 1, std::max(0, nontemporal));
-  return ECGPU_OK;
-}
-
-ECGPU_API int ecgpu_plan_launch(ecgpu_plan* p, void* stream) {
-  if (!p) return fail(ECGPU_ERR_ARG, "ecgpu_plan_launch: null plan");
-  return plan_launch(p, static_cast<hipStream_t>(stream));
-}
-
-ECGPU_API void ecgpu_plan_destroy(ecgpu_plan* p) { plan_free(p); }
-
-ECGPU_API int ecgpu_set_devices(int n, const int* devices) {
-  if (n < 0 || (n > 0 && !devices)) return fail(ECGPU_ERR_ARG, "ecgpu_set_devices: bad arguments");
-  for (int i = 0; i < n; ++i)
-    if (devices[i] < 0) return fail(ECGPU_ERR_ARG, "ecgpu_set_devices: negative device");
-  const int visible = visible_devices();
-  if (const int bad = invisible_entry(std::vector<int>(devices, devices + n), visible); bad >= 0)
-    return fail(ECGPU_ERR_ARG, "ecgpu_set_devices: device " + std::to_string(bad) + " is not visible (" +
-                                   std::to_string(visible) + " visible)");
-  (void)device_list();  // the environment's list is read first, so this call overrides it
-  std::lock_guard<std::mutex> lk(g_devices_mu);
-  g_devices = n > 0 ? std::make_shared<const std::vector<int>>(devices, devices + n) : nullptr;
-  return ECGPU_OK;
-}
-
-ECGPU_API int ecgpu_get_devices(int* out, int cap) {
-  const auto list = device_list();
-  const int n = list ? int(list->size()) : 0;
-  for (int i = 0; i < n && i < cap && out; ++i) out[i] = (*list)[size_t(i)];
-  return n;
-}
-
-ECGPU_API int ecgpu_call_device(void) { return host_call_device(); }
-
-ECGPU_API int ecgpu_device_pci_bus_id(int device, char* buf, int len) {
-  if (!buf || len < 13) return fail(ECGPU_ERR_ARG, "ecgpu_device_pci_bus_id: buffer of >= 13 bytes required");
-  ECGPU_HIP(hipDeviceGetPCIBusId(buf, len, device));
-  return ECGPU_OK;
-}
-
-ECGPU_API int ecgpu_host_register(void* ptr, int64_t bytes) {
-  if (!ptr || bytes <= 0) return fail(ECGPU_ERR_ARG, "ecgpu_host_register: bad arguments");
-  ECGPU_HIP(hipHostRegister(ptr, size_t(bytes), hipHostRegisterDefault));
-  return ECGPU_OK;
-}
-
-ECGPU_API int ecgpu_host_unregister(void* ptr) {
-  if (!ptr) return fail(ECGPU_ERR_ARG, "ecgpu_host_unregister: null");
-  ECGPU_HIP(hipHostUnregister(ptr));
-  return ECGPU_OK;
-}
-
-ECGPU_API int ecgpu_encode_batch(int k, int m, const int* matrix, int stripes, const uint8_t* const* data,
-                                 uint8_t* const* coding, int64_t size, void* stream) {
-  if (k <= 0 || m <= 0 || !matrix || stripes < 0 || size < 0 || (stripes && (!data || !coding)))
-    return fail(ECGPU_ERR_ARG, "ecgpu_encode_batch: bad arguments");
-  if (int rc = ecgpu_plan_check_buffers(m, k, stripes, data, coding, size)) return rc;
-  ecgpu_plan* p = ecgpu_plan_create(m, k, matrix, -1);
-  if (!p) return ECGPU_ERR_HIP;
-  int rc = plan_bind(p, stripes, data, coding, size, static_cast<hipStream_t>(stream));
-  if (rc == ECGPU_OK) rc = plan_launch(p, static_cast<hipStream_t>(stream));
-  if (rc == ECGPU_OK && stream) {
-    hipError_t e = hipStreamSynchronize(static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) rc = fail(ECGPU_ERR_HIP, hipGetErrorString(e));
-  } else if (rc == ECGPU_OK) {
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) rc = fail(ECGPU_ERR_HIP, hipGetErrorString(e));
-  }
-  plan_free(p);
-  return rc;
-}
 
 namespace {
 bool valid_w(int w) { return w == 8 || w == 16 || w == 32; }

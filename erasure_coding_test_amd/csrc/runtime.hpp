@@ -1,7 +1,13 @@
 // runtime.hpp -- internal interface shared by the runtime's translation
 // units (not installed; the public surface is include/ecgpu.h):
-//   ecgpu_runtime.hip  plans, kernel dispatch, contexts, staging of host
-//                      buffers, synchronous calls and their C ABI
+//   plans.hip          plan lifecycle (table upload, bind, free) and its C ABI
+//   devices.hip        HIP error classification, device selection and its C ABI
+//   contexts.hip       the synchronous calls' context pool and staging buffers
+//   host_memory.hip    where a buffer lives, shard copies, host registration
+//   ecgpu_runtime.hip  staging of host buffers, synchronous calls and their
+//                      C ABI
+//   dispatch_w8.hip    plan tables and launches, w = 8
+//   dispatch_wide.hip  plan tables and launches, w = 16 / 32
 //   accum.hip          HBM-resident ECX parity accumulators
 //   pipeline.hip       host-memory pipelines and multi-device groups
 //   packets.hip        GF(2) bit-matrix / schedule coding
@@ -11,8 +17,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <list>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -20,6 +28,7 @@
 
 #include "ecgpu.h"
 #include "gf_kernels.hpp"
+#include "gf_spec.hpp"
 #include "knobs.hpp"
 #include "planner.hpp"
 
@@ -87,6 +96,7 @@ enum class Where { kHost, kDevice, kUnknown };
 Where where(const void* p);
 // Every buffer host memory, positively known (the CPU executor may run the call).
 bool all_host(const std::vector<void*>& bufs);
+bool all_host(const FusedOp& op);
 
 #define ECGPU_HIP(expr)                                 \
   do {                                                  \
@@ -106,9 +116,19 @@ struct DeviceGuard {
   }
 };
 
+// ---- devices (devices.hip) ----------------------------------------------------
 int current_device();
+// Visible devices, or 0 when HIP cannot tell.
+int visible_devices();
+// A forced ECGPU_DEVICE that names a visible device, else -1.
+int forced_device();
+// The ECGPU_DEVICES / ecgpu_set_devices list, null when unset.
+std::shared_ptr<const std::vector<int>> device_list();
+// The device a synchronous call on host memory runs on: a forced
+// ECGPU_DEVICE, else this thread's device from the list, else the current one.
+int host_call_device();
 // The device a synchronous call on these buffers runs on (ECGPU_DEVICE,
-// ECGPU_DEVICES, or the current device; ecgpu_runtime.hip).
+// ECGPU_DEVICES, or the current device).
 int call_device(const std::vector<void*>& a, const std::vector<void*>& b);
 
 // ---- kernel launches -----------------------------------------------------------
@@ -128,9 +148,11 @@ int unit_variant(const std::vector<uint32_t>& coef, int K, int r0, int R);
 unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes = 0);
 bool cap_for(int K, int R, int mul_terms);
 
-// ---- plans --------------------------------------------------------------------
+// ---- plans (plans.hip) --------------------------------------------------------
+// A store-policy request clamped to the policies the kernels have (gf_spec.hpp).
+inline int clamp_store_policy(int nt) { return std::min(kStorePolicies - 1, std::max(0, nt)); }
 void plan_free(ecgpu_plan* p);
-// one asynchronous upload of a plan's coefficient tables (ecgpu_runtime.hip);
+// one asynchronous upload of a plan's coefficient tables;
 // launches wait for it through plan_wait_tables
 int plan_upload_tables(ecgpu_plan* p, std::vector<uint8_t>&& host);
 int plan_wait_tables(ecgpu_plan* p, hipStream_t stream);
@@ -149,7 +171,7 @@ int plan_bind(ecgpu_plan* p, int stripes, const uint8_t* const* src, uint8_t* co
               hipStream_t stream, bool keep_alive = false);
 int plan_launch(ecgpu_plan* p, hipStream_t stream);
 
-// ---- contexts of the synchronous calls ----------------------------------------
+// ---- contexts of the synchronous calls (contexts.hip) -------------------------
 struct PlanKey {
   int rows, nsrc, w, kind, nt;  // kind / nt: the engine and store-policy knobs the plan was made under
   std::vector<uint32_t> coef;
@@ -187,14 +209,14 @@ int ensure_bounce(Ctx* c, size_t bytes);
 int ensure_zc(Ctx* c, size_t bytes);
 int ensure_stage(Ctx* c, size_t bytes);
 
-// ---- host memory --------------------------------------------------------------
-bool zero_copy_pinned();
+// ---- host memory (host_memory.hip) --------------------------------------------
 int classify(const void* p, int device, bool* on_device);
 bool host_mapped(const void* p, size_t bytes, void** dev);
 bool is_pinned(const void* p);
 int copy_shards(bool h2d, uint8_t* d0, size_t dstride, const std::vector<char*>& hp, size_t bytes, hipStream_t s);
 
-// ---- synchronous execution ----------------------------------------------------
+// ---- synchronous execution (ecgpu_runtime.hip) --------------------------------
+bool zero_copy_pinned();
 void add_stats(const FusedOp& op);
 bool inline_ok(const FusedOp& op, int64_t size);
 int launch_inline(const FusedOp& op, const std::vector<const uint8_t*>& sp, const std::vector<uint8_t*>& dp,

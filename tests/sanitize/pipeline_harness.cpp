@@ -3,7 +3,8 @@
 // machine, the pipeline groups' member queues, the context pool, per-device
 // lazy objects) driven on a FAKE device, built with -fsanitize=thread by
 // tests/test_sanitizers.py.  No HIP: host_sync.hpp is the exact code that
-// libecgpu's pipeline.hip and ecgpu_runtime.hip instantiate with HIP ops.
+// libecgpu's pipeline.hip, contexts.hip (IdlePool) and plans.hip (PerDevice)
+// instantiate with HIP ops.
 //
 // The fake device: every stream is a thread running its queue in order, each
 // operation after a random delay; an event is a counter pair (recorded /

@@ -63,7 +63,8 @@ def test_kernel_families_have_their_own_build_ids(tmp_path):
     b = _build_module()
     base = b.build_ids()
     for name in ("gf_kernels_wide.hpp", "gf_kernels_packets.hpp", "dispatch_wide.hip", "wide_spec.hip",
-                 "packets.hip", "diag_kernels_w8.hpp", "diag_kernels.hip", "ecgpu_runtime.hip", "cpu_fallback.cpp"):
+                 "packets.hip", "diag_kernels_w8.hpp", "diag_kernels.hip", "ecgpu_runtime.hip", "plans.hip",
+                 "devices.hip", "contexts.hip", "host_memory.hip", "cpu_fallback.cpp"):
         ids = _ids_with_edit(b, tmp_path, name)
         assert ids["kernels"] == base["kernels"], name
         assert ids["build"] != base["build"] or name.startswith("diag_kernels"), name

@@ -172,7 +172,7 @@ def test_real_hip_error_hbm_full_completes_on_the_cpu_gpu():
     """A genuine HIP failure, not an injected one: HBM filled by hipMalloc
     until it fails, then the client's C3 4 MiB pageable encode +
     decode{0,1,2,3} through the mangled names -- the library's staging
-    hipMalloc fails (csrc/ecgpu_runtime.hip ensure_stage) and the calls
+    hipMalloc fails (csrc/contexts.hip ensure_stage) and the calls
     complete on the CPU, bit-exact against the golden digests; the device is
     not marked lost (out of memory is not sticky).  With the knob at 0 the
     unchanged caller exits 1 (VERDICT r5 next #2)."""

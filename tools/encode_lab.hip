@@ -274,7 +274,7 @@ struct Variant {
   int cols = 0;       // > 0: columns per workgroup when it is not bs (VEC > 1 forms)
 };
 
-// builds the production 3-bit-slice tables (ecgpu_runtime.hip build_tables)
+// builds the production 3-bit-slice tables (dispatch_w8.hip build_tables)
 static void build_p3(int c, uint32_t* p3) {
   const auto& T = gf8().mul[c & 0xFF];
   for (int i = 0; i < kP3Words; ++i) p3[i] = 0;
@@ -378,7 +378,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
   std::vector<uint32_t> ptab(size_t(m) * k * kP3Words);
   for (int r = 0; r < m; ++r)
     for (int j = 0; j < k; ++j) build_p3(M[r * k + j], &ptab[(size_t(r) * k + j) * kP3Words]);
-  // the LDS engine's per-coefficient nibble tables (ecgpu_runtime.hip): c*v, then c*(v << 4)
+  // the LDS engine's per-coefficient nibble tables (dispatch_w8.hip build_tables): c*v, then c*(v << 4)
   std::vector<uint8_t> ntab(size_t(m) * k * 32);
   for (int r = 0; r < m; ++r)
     for (int j = 0; j < k; ++j)
@@ -433,7 +433,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
   using V = Variant;
   const void* const vperm = reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>);
   const void* const ldsk = reinterpret_cast<const void*>(&gf_apply_lds<k, m>);
-  const int cap = k + m <= 9 ? 4 : 3;  // ecgpu_runtime.hip residency_lds_bytes
+  const int cap = k + m <= 9 ? 4 : 3;  // dispatch_w8.hip residency_lds_bytes
   const unsigned lds_cap = ((unsigned(163840 / cap) & ~511u) - 128u * k - 4096u) & ~4095u;
   std::vector<Variant> vs = g_sched == 2 ? std::vector<Variant>{  // the R = 1 levers (lost parity)
       V{"prod", vperm, 256, cap},
@@ -614,7 +614,7 @@ int skew_ab(int stripes, int kib, const std::vector<int>& skews, int rounds, int
   int dev = 0, lds_cu = 0;
   CK(hipGetDevice(&dev));
   CK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-  const int blocks = k + m <= 9 ? 4 : 3;  // ecgpu_runtime.hip residency_lds_bytes
+  const int blocks = k + m <= 9 ? 4 : 3;  // dispatch_w8.hip residency_lds_bytes
   const unsigned lds = unsigned(lds_cu / blocks) & ~511u;
   constexpr int U = kUnitCol0 | kUnitRow0;
   const void* fn = reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>);

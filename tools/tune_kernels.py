@@ -38,7 +38,7 @@ def tables(coefs):
         for p in range(4):
             q.append(sum(gm(c, e << (2 * p), 8) << (8 * e) for e in range(4)))
         nib += [gm(c, x, 8) for x in range(16)] + [gm(c, x << 4, 8) for x in range(16)]
-        # P3 layout (ecgpu_runtime.hip build_tables): T0lo T0hi T1lo T1hi T2 pad pad pad
+        # P3 layout (dispatch_w8.hip build_tables): T0lo T0hi T1lo T1hi T2 pad pad pad
         w = lambda vals: sum(v << (8 * e) for e, v in enumerate(vals))
         t0 = [gm(c, e, 8) for e in range(8)]
         t1 = [gm(c, e << 3, 8) for e in range(8)]

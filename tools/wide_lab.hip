@@ -497,7 +497,7 @@ int main(int argc, char** argv) {
   const int R = m, K = k;
   // Vandermonde coding matrix of the reference (reed_sol.cpp:63-84)
   int* M = vandermonde_coding_matrix(k, m, w);
-  // per-coefficient nibble tables (ecgpu_runtime.hip build_wide_nib_tables)
+  // per-coefficient nibble tables (dispatch_wide.hip build_wide_nib_tables)
   std::vector<uint32_t> wtab(size_t(R) * K * kNibWords);
   for (int r = 0; r < R; ++r)
     for (int j = 0; j < K; ++j) {
