@@ -54,6 +54,7 @@ SIGNATURES = {
     "ecgpu_get_devices": (c_int, [c_int_p, c_int]),
     "ecgpu_call_device": (c_int, []),
     "ecgpu_engine_launches": (c_int64, [c_int]),
+    "ecgpu_packet_launches": (c_int64, [c_int]),
     "ecgpu_galois_single_multiply": (c_int, [c_int, c_int, c_int]),
     "ecgpu_galois_single_divide": (c_int, [c_int, c_int, c_int]),
     "ecgpu_galois_inverse": (c_int, [c_int, c_int]),

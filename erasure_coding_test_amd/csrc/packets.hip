@@ -46,6 +46,11 @@ constexpr int kMaxPacketRow = (1 << 20) - 1;
 
 constexpr int kPacketRows = 32;  // output packet rows per launch (uint32 masks)
 
+// Packet launches per kernel (ecgpu_packet_launches): 0 bytes, 1 8-B lanes,
+// 2 unpipelined 16-B, 3 pipelined 16-B, 4 unit form, 5 zero-fill of a group.
+constexpr int kPacketKinds = 6;
+std::atomic<int64_t> g_packet_launches[kPacketKinds];
+
 // The map of a w = 8 Vandermonde bit-matrix encode, exactly (the unit form
 // gf_xor_packets16u relies on it): 32 output rows, sources device-major in
 // whole devices of 8 bits, bit b of every device feeding output row b (the
@@ -245,31 +250,39 @@ int packets_on_ctx(Ctx* c, const FusedOp& op, const std::vector<char*>& ptrs, in
     a.cpp = wide16 ? ps / 16 : aligned ? ps / 8 : ps;
     a.ncols = nsp * a.cpp;
     if (nsrc == 0) {  // every output packet is zero
+      g_packet_launches[5].fetch_add(1, std::memory_order_relaxed);
       for (int r = 0; r < R; ++r)
         ECGPU_HIP(hipMemset2DAsync(db[size_t(g0 * kPacketRows + r)], size_t(nsp > 1 ? dstride : ps), 0, size_t(ps),
                                    size_t(nsp), c->stream));
       continue;
     }
     void* fn = nullptr;
+    int counted = 0;
     if (wide16 && packet_kind == 0 && R == kPacketRows &&
-        unit_packet_map(masks.data() + size_t(g0) * nsrc, nsrc))
+        unit_packet_map(masks.data() + size_t(g0) * nsrc, nsrc)) {
       fn = reinterpret_cast<void*>(&dev::gf_xor_packets16u<32>);
-    else if (wide16 && packet_kind == 2)
+      counted = 4;
+    } else if (wide16 && packet_kind == 2) {
+      counted = 2;
       fn = R <= 8    ? reinterpret_cast<void*>(&dev::gf_xor_packets16<8, 8>)
            : R <= 16 ? reinterpret_cast<void*>(&dev::gf_xor_packets16<16, 8>)
                      : reinterpret_cast<void*>(&dev::gf_xor_packets16<32, 8>);
-    else if (wide16)
+    } else if (wide16) {
+      counted = 3;
       fn = R <= 8    ? reinterpret_cast<void*>(&dev::gf_xor_packets16p<8>)
            : R <= 16 ? reinterpret_cast<void*>(&dev::gf_xor_packets16p<16>)
                      : reinterpret_cast<void*>(&dev::gf_xor_packets16p<32>);
-    else
+    } else {
+      counted = aligned ? 1 : 0;
       fn = aligned ? (R <= 8    ? reinterpret_cast<void*>(&dev::gf_xor_packets<8>)
                       : R <= 16 ? reinterpret_cast<void*>(&dev::gf_xor_packets<16>)
                                 : reinterpret_cast<void*>(&dev::gf_xor_packets<32>))
                    : reinterpret_cast<void*>(&dev::gf_xor_packets_bytes);
+    }
     void* args[] = {&a};
     const dim3 grid(unsigned((a.ncols + dev::kBlock - 1) / dev::kBlock));
     ECGPU_HIP(hipLaunchKernel(fn, grid, dim3(dev::kBlock), args, 0, c->stream));
+    g_packet_launches[counted].fetch_add(1, std::memory_order_relaxed);
   }
   if (via_temp)
     for (int r = 0; r < rows; ++r) {
@@ -353,6 +366,10 @@ void record_schedule(PacketTracker& t, int** ops, int64_t ps, int64_t nsp) {
 }  // namespace
 
 extern "C" {
+
+ECGPU_API int64_t ecgpu_packet_launches(int kind) {
+  return kind >= 0 && kind < kPacketKinds ? g_packet_launches[kind].load(std::memory_order_relaxed) : -1;
+}
 
 ECGPU_API int ecgpu_jerasure_bitmatrix_dotprod(int k, int w, int* bitmatrix_row, int* src_ids, int dest_id,
                                                char** data_ptrs, char** coding_ptrs, int size, int packetsize) {

@@ -117,6 +117,11 @@ ECGPU_API int ecgpu_call_device(void);
 /* Specialised w = 8 column launches so far per engine (kind =
  * ECGPU_KERNEL_PERM / ECGPU_KERNEL_LDS): which engine a knob setting reached. */
 ECGPU_API int64_t ecgpu_engine_launches(int kind);
+/* GF(2) packet launches so far per kernel: kind 0 gf_xor_packets_bytes, 1
+ * gf_xor_packets (8-B lanes), 2 gf_xor_packets16, 3 gf_xor_packets16p, 4
+ * gf_xor_packets16u (unit form), 5 the zero-fill of a 32-row group whose
+ * outputs all fold to zero (once per group); -1 for any other kind. */
+ECGPU_API int64_t ecgpu_packet_launches(int kind);
 
 /* ------------------------------------- GF(2^w) scalar ops (host only) --- */
 ECGPU_API int ecgpu_galois_single_multiply(int a, int b, int w); /* galois.cpp:322-360 */
