@@ -337,6 +337,12 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
   // resident blocks per CU at 160 KiB / bytes (occupancy experiments).
   const char* lds_env = std::getenv("ECGPU_DIAG_LDS");
   const unsigned lds = lds_env ? unsigned(std::atoi(lds_env)) : 0u;
+  // 2 blocks per CU is 80 KiB, above the 64 KiB a launch may ask for by
+  // default: raise the function's limit (up to the CU's 160 KiB).
+  if (lds > 65536u && lds <= 163840u &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) !=
+          hipSuccess)
+    return -3;
   return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid, dim3(256), args, lds,
                          static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -3;
 }

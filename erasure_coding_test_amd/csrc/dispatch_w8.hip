@@ -61,23 +61,33 @@ KernelFn generic_fn(int R) {
 
 
 // Residency cap for the streaming kernels.  Fewer resident workgroups per CU
-// means fewer DRAM pages open at once across the chip: with each lane reading
-// K shards and writing R, the uncapped kernel (VGPR-limited to 7 blocks/CU)
-// keeps ~28k distinct 4 KiB shard chunks in flight.  What matters is the
-// number of shard streams per lane, K + R: a sweep over eight encode and
-// decode shapes (K + R = 5..16, 64 KiB..16 MiB shards, 3 interleaved rounds,
-// profiles/r02_residency_sweep.json) has 4 blocks/CU best or within 0.3 % of
-// the best for K + R <= 9 and 3 blocks/CU for K + R >= 10; never capping is
-// the worst or near it everywhere (-1.5 % to -7 %).  A launch dense in GF
-// multiplies (decode{0,1,2,3}: 40 non-unit coefficients over 14 shards)
-// needs the occupancy to hide its VALU work and loses 7 %, so such launches
-// stay uncapped (cap_for).  The cap is an unused dynamic LDS allocation of
-// LDS_per_CU / blocks (rounded down to 512 B).  A kernel with static LDS of
+// means fewer DRAM pages open at once across the chip: each lane reads K
+// shards and writes R, and a kernel left to its register limit (8 workgroups
+// per CU for the 46-64 VGPR kernels) keeps ~30k distinct 4 KiB shard chunks in
+// flight.  What matters is the number of shard streams per lane, K + R: a
+// sweep over eight encode and decode shapes (K + R = 5..16, 64 KiB..16 MiB
+// shards, 3 interleaved rounds, profiles/r02_residency_sweep.json) has
+// 4 blocks/CU best or within 0.3 % of the best for K + R <= 9 and 3 blocks/CU
+// for K + R >= 10.  That sweep's R >= 3 rows ran kernels of 155-209 VGPRs,
+// which sit at 2-3 per CU under any cap; with the sequential body (50-105
+// VGPRs, gf_kernels_w8.hpp) the cap governs them too, and the same rule holds
+// (profiles/r07_residency_lab.json: RS(10,4) encode 873-876 us at 2 and 3
+// per CU, 959-987 at 4-6, 1011 uncapped; RS(6,3) 752-762 at 2-5).
+// A 256-thread workgroup puts one wave on each SIMD, so a cap of N per CU is
+// real only while the kernel fits N waves on a SIMD: every specialised
+// kernel must reach kMinWavesPerSimd (tests/test_kernel_resources.py
+// compiles the bench's instantiations and checks).  The cap is an unused
+// dynamic LDS allocation of LDS_per_CU / blocks (rounded down to 512 B); at
+// most kCapMaxBlocks per CU, so never above the 64 KiB a launch may ask for
+// without raising the function's limit.  A kernel with static LDS of
 // its own (the LDS engine's tables) gets that much less and a further 4 KiB
 // margin, rounded down to 4 KiB: RS(10,4) at "3 per CU" with 1,280 B of
 // tables, dynamic 52,736 B (1.8 KiB spare) ran at 2 per CU's speed (989 us),
 // 40,960-49,152 B at 902-905 (tools/encode_lab.hip --lds 2).
 // ECGPU_BLOCKS_PER_CU fixes the block count (0 = never cap).
+constexpr int kCapMaxBlocks = 4;     // K + R <= 9; one fewer above
+constexpr int kMinWavesPerSimd = 4;  // what every specialised v_perm kernel's VGPR count must allow
+static_assert(kMinWavesPerSimd >= kCapMaxBlocks, "a cap above the register limit is a no-op");
 unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes) {
   static std::once_flag once;
   static int per_cu = 0;
@@ -86,7 +96,7 @@ unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes) {
       per_cu = 0;
   });
   const int fixed = knob(Knob::kBlocksPerCu);
-  const int blocks = fixed >= 0 ? fixed : (streams <= 9 ? 4 : 3);
+  const int blocks = fixed >= 0 ? fixed : (streams <= 9 ? kCapMaxBlocks : kCapMaxBlocks - 1);
   if (blocks <= 0 || per_cu <= 0) return 0;
   const unsigned total = unsigned(per_cu / blocks) & ~511u;
   const unsigned reserve = static_bytes ? static_bytes + 4096u : 0u;
@@ -99,15 +109,21 @@ unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes) {
 // back-to-back context, DESIGN.md §5, profiles/r01_policy_ab.json):
 //   * stores non-temporal (loads always are): bench step +4 %, RS(10,4)
 //     encode 0.947 -> 0.889 ms, dense decode +9 %, RS(12,4) +6 %;
-//   * residency cap unless the launch is dense in GF multiplies (more than
-//     2.5 non-unit coefficients per shard touched): decode{0} +9 %, RS(6,3)
-//     +6 %; the 40-multiply decode{0,1,2,3} needs the occupancy (-7 % capped).
+//   * residency cap: always for the sequential body (`seq`: a specialised
+//     v_perm launch of dev::kSeqMinRows rows or more) -- at its 50-105 VGPRs an
+//     uncapped launch runs 4-8 workgroups per CU and loses 10-15 % (dense
+//     decode{0,1,2,3}: 894-899 us at 3 per CU, 997 uncapped; the 155-VGPR
+//     body it replaces ran 904-918 at its register limit of 3, which is what
+//     "needs the occupancy" used to mean);
+//   * for the other kernels (R <= 2, generic K, the LDS engine) unless the
+//     launch is dense in GF multiplies (more than 2.5 non-unit coefficients
+//     per shard touched): decode{0} +9 % capped.
 // The store policy is the plan's `nt` field (0 plain, 1 nt -- the default;
 // ECGPU_NT, ecgpu_plan_set_kernel); the cap knob (ECGPU_CAP: 0 = never,
 // 1 = always) overrides the cap rule.
-bool cap_for(int K, int R, int mul_terms) {
+bool cap_for(int K, int R, int mul_terms, bool seq) {
   const int v = knob(Knob::kCap);
-  return v < 0 ? 2 * mul_terms <= 5 * (K + R) : (v != 0);
+  return v < 0 ? (seq || 2 * mul_terms <= 5 * (K + R)) : (v != 0);
 }
 
 // Per-coefficient tables.  PERM: word p holds c*(e << 2p) in byte e.  LDS:
@@ -189,7 +205,7 @@ int plan_launch(ecgpu_plan* p, hipStream_t stream) {
     // Both engines follow the cap rule; the LDS engine's allocation leaves room
     // for its K * 128 B of tables (tools/encode_lab.hip --lds: RS(10,4) encode
     // 1008 us uncapped, 902 at 3 per CU, v_perm 890).
-    const bool cap = cap_for(K, R, mul_terms);
+    const bool cap = cap_for(K, R, mul_terms, spec && !use_lds && R >= dev::kSeqMinRows);
     const unsigned static_lds = use_lds && spec ? unsigned(K) * 32u * 4u : 0u;
     uint64_t unit = 0, zero = 0;
     if (spec)

@@ -248,10 +248,26 @@ __device__ __forceinline__ void combine_store(const ApplyArgs& a, const u32x4 (&
   for (int r = 0; r < R; ++r) store16t<NTS>(dp[r], col, acc[r]);
 }
 
+// Launches of kSeqMinRows output rows or more take the sequential form of
+// gf_apply_body, whose load schedule is a window: load_window<K>() source
+// loads are issued before the first multiply and one more as each source is
+// consumed.  Interleaved in one process at 3 workgroups per CU
+// (tools/encode_lab.hip --resid 2, profiles/r07_residency_lab.json): a
+// window of 4-6 beats every load first by 1.6-3.5 % on RS(10,4) at 1, 4 and
+// 16 MiB shards and by 0-2 % on RS(12,4) at 1 and 4 MiB, but loses 9 % on
+// RS(12,4) at 16 MiB (C5: 1071 vs 981 us), the one shape where a late load
+// costs.  Hence 6 up to K = 10 and every load first above; K <= 6 is the same
+// kernel either way.  (Two points per K: a rule by shard size would need a
+// second instantiation of every kernel.)
+constexpr int kSeqMinRows = 3;
+template <int K>
+constexpr int load_window() { return K <= 10 ? 6 : K; }
+
 // Lane l of block b handles the 16-byte columns (b*VEC + v)*256 + l, v < VEC,
-// of every shard of stripe s: all K*VEC loads are issued before any
-// arithmetic, then R*VEC stores.  NT: bit 0 = non-temporal loads, NT >> 1 =
-// store policy of store16t (VEC == 1; the VEC > 1 probe form follows a.nt).
+// of every shard of stripe s; R < kSeqMinRows and VEC > 1: all K*VEC loads
+// are issued before any arithmetic, then R*VEC stores.  NT: bit 0 =
+// non-temporal loads, NT >> 1 = store policy of store16t (VEC == 1; the
+// VEC > 1 probe form follows a.nt).
 template <int K, int R, int UNITS, int VEC, int SLICES = 3, int NT = 3>
 __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
   const unsigned cblk = a.stripe_fast ? blockIdx.y : blockIdx.x;
@@ -266,9 +282,57 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
 #pragma unroll
   for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
 
-  if constexpr (VEC == 1) {
-    // Single column per lane (production): straight-line form, which keeps
-    // the register allocation low (69 VGPRs for RS(10,4)).
+  if constexpr (VEC == 1 && SLICES == 3 && R >= kSeqMinRows) {
+    // Three or four output rows (production): the sources are consumed one
+    // after the other, written out here in the kernel body.  The same
+    // arithmetic through combine3 -- x[] and acc[] handed down by reference
+    // -- compiles to 177 VGPRs for RS(10,4) encode, 209 for RS(12,4) and 155
+    // for a dense 4 x 10 map: two or three waves per SIMD, so two or three
+    // 256-thread workgroups per CU whatever the dispatcher's cap asks for.
+    // This form needs 50-82 VGPRs for those shapes (K = 16 dense: 105) and no
+    // scratch, with the same v_perm / v_bitop3 counts (324 / 188 for RS(10,4)
+    // encode), so the residency is the dispatcher's choice (dispatch_w8.hip
+    // cap_for; tests/test_kernel_resources.py holds the budget).  Scheduling
+    // fences pin the load schedule, which the compiler otherwise derives from
+    // its register target: G = load_window<K>() loads go out first, the load
+    // of source j + G just before source j is consumed.
+    constexpr int G = load_window<K>();
+    const kconst_u32* ptab = (const kconst_u32*)a.ptab;  // C cast: generic -> constant (scalar loads)
+    u32x4 x[K];
+#pragma unroll
+    for (int j = 0; j < K && j < G; ++j) x[j] = load16t<NT & 1>(sp[j], col0);
+    Xacc xa[R][4];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      __builtin_amdgcn_sched_barrier(0);
+      if (j + G < K) x[j + G] = load16t<NT & 1>(sp[j + G], col0);
+      Sel3 sl[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) sl[c] = sel3(x[j][c]);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (is_unit<UNITS>(r, j)) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) xa[r][c].add(x[j][c]);
+        } else {
+          const kconst_u32* t = ptab + (r * K + j) * kP3Words;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) mac3(xa[r][c], t, sl[c]);
+        }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      u32x4 o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = xa[r][c].value();
+      store16t<(NT >> 1)>(dp[r], col0, o);
+    }
+    return;
+  } else if constexpr (VEC == 1) {
+    // Single column per lane, one or two output rows (46-58 VGPRs for the
+    // R = 1 decodes) and the 2-bit-slice diagnostic form.
     u32x4 x[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) x[j] = load16t<NT & 1>(sp[j], col0);

@@ -146,7 +146,7 @@ inline hipError_t launch(KernelFn fn, dim3 grid, dim3 block, ecgpu::dev::ApplyAr
 // whether a launch takes the cap
 int unit_variant(const std::vector<uint32_t>& coef, int K, int r0, int R);
 unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes = 0);
-bool cap_for(int K, int R, int mul_terms);
+bool cap_for(int K, int R, int mul_terms, bool seq = false);  // seq: the sequential R >= 3 body of gf_apply
 
 // ---- plans (plans.hip) --------------------------------------------------------
 // A store-policy request clamped to the policies the kernels have (gf_spec.hpp).

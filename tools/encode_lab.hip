@@ -12,6 +12,9 @@
 //   tools/encode_lab.bin [--stripes 96] [--rounds 7] [--reps 10] [--skew-kib N]
 //   tools/encode_lab.bin --skews 10,12,8,6 [--k 12 --m 4 --mib 16 --stripes 24]
 //       the production launch on one slab per shard-stride skew (KiB), interleaved
+//   tools/encode_lab.bin --resid 1|2 [--dense 1] [--k 12 --m 4 --mib 16 --stripes 24]
+//       1: register budgets x residency caps of the R >= 3 body, with the XOR stream probe at every cap;
+//       2: the sequential body's load window (4 / 6 / 8 / all loads first) at 2 / 3 / 4 per CU
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +23,7 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gf_host.hpp"
@@ -255,6 +259,148 @@ __global__ __launch_bounds__(256) void enc_sb(ApplyArgs a) {
   __builtin_amdgcn_sched_barrier(0);
   combine_store<K, R, UNITS, 3, 1>(a, x, dp, col);
 }
+// ---- residency lab (--resid 1 / 2): which register budget and which cap
+// the R >= 3 kernels should run at.  Until this lab the production body went
+// through combine3 with x[] and acc[] by reference and compiled to 177 VGPRs
+// for RS(10,4) encode: two waves per SIMD, whatever cap the dispatcher asked
+// for.  That body is kept here as enc_bs<.., 256> ("byref").
+//   enc_par<WV>: the by-reference body under amdgpu_waves_per_eu(WV, WV)
+//                (WV = 3: 168 VGPRs, no scratch)
+//   enc_seq<WV>: the sources consumed one after the other, every load issued
+//                first, the accumulators local to the kernel body (enc_seq0:
+//                no register attribute at all)
+//   enc_win<G>:  the same with its load window pinned (production since:
+//                gf_kernels_w8.hpp load_window)
+//   xor_mix:     the launch's K nt loads and R nt stores with one XOR per
+//                source (diag_kernels.hip diag_xor_mix), so the stream
+//                pattern can be timed at the kernel's own residency
+template <int K, int R, int UNITS>
+__device__ __forceinline__ void seq_body(const ApplyArgs& a) {
+  const int64_t col = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (col >= a.nvec) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* dp[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
+  const kconst_u32* ptab = (const kconst_u32*)a.ptab;
+  u32x4 x[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) x[j] = load16t<1>(sp[j], col);
+  Xacc xa[R][4];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    Sel3 sl[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sl[c] = sel3(x[j][c]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (is_unit<UNITS>(r, j)) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xa[r][c].add(x[j][c]);
+      } else {
+        const kconst_u32* t = ptab + (r * K + j) * kP3Words;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) mac3(xa[r][c], t, sl[c]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    u32x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = xa[r][c].value();
+    store16t<1>(dp[r], col, o);
+  }
+}
+template <int K, int R, int UNITS, int WV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV, WV))) void enc_seq(ApplyArgs a) {
+  seq_body<K, R, UNITS>(a);
+}
+template <int K, int R, int UNITS>
+__global__ __launch_bounds__(256) void enc_seq0(ApplyArgs a) {
+  seq_body<K, R, UNITS>(a);
+}
+// The sequential form with its load schedule pinned by scheduling fences: G
+// loads are issued first, and the load of source j + G goes out just before
+// source j is consumed (G >= K: every load first).  Left alone the compiler
+// picks the window from its register target -- 8 loads first and the rest
+// one memory latency apart without an attribute, every load first under
+// amdgpu_waves_per_eu(4, 4) -- and the two differ by 3 % (C3) to 8 % (C5).
+template <int K, int R, int UNITS, int G>
+__global__ __launch_bounds__(256) void enc_win(ApplyArgs a) {
+  const int64_t col = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (col >= a.nvec) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* dp[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
+  const kconst_u32* ptab = (const kconst_u32*)a.ptab;
+  u32x4 x[K];
+#pragma unroll
+  for (int j = 0; j < K && j < G; ++j) x[j] = load16t<1>(sp[j], col);
+  Xacc xa[R][4];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (j + G < K) x[j + G] = load16t<1>(sp[j + G], col);
+    Sel3 sl[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) sl[c] = sel3(x[j][c]);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (is_unit<UNITS>(r, j)) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) xa[r][c].add(x[j][c]);
+      } else {
+        const kconst_u32* t = ptab + (r * K + j) * kP3Words;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) mac3(xa[r][c], t, sl[c]);
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    u32x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = xa[r][c].value();
+    store16t<1>(dp[r], col, o);
+  }
+}
+template <int K, int R, int UNITS, int WV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV, WV))) void enc_par(ApplyArgs a) {
+  const int64_t col = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (col >= a.nvec) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* dp[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
+  u32x4 x[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) x[j] = load16t<1>(sp[j], col);
+  combine_store<K, R, UNITS, 3, 1>(a, x, dp, col);
+}
+template <int K, int R>
+__global__ __launch_bounds__(256) void xor_mix(ApplyArgs a) {
+  const int64_t col = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (col >= a.nvec) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* dp[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + r];
+  u32x4 x[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) x[j] = load16t<1>(sp[j], col);
+  u32x4 acc = x[0];
+#pragma unroll
+  for (int j = 1; j < K; ++j) acc ^= x[j];
+#pragma unroll
+  for (int r = 0; r < R; ++r) store16t<1>(dp[r], col, acc);
+}
 }  // namespace lab
 
 bool g_early0 = false;  // --early0 1: skew mode also times lab::enc_early0 on every slab
@@ -262,6 +408,7 @@ bool g_vec2 = false;    // --vec2 1: ... and the production body with two column
 bool g_dense = false;   // --dense 1: a C4-like dense 4 x 10 map (no 0 / 1 coefficients) instead of the encode
 int g_sched = 0;        // --sched 1: production vs lab::enc_sb (all loads issued before the arithmetic)
 bool g_lost = false;    // --lost 1 (with --m 1): the lost-parity decode's map -- row 2 of the RS(k,4) Vandermonde matrix
+int g_resid = 0;        // --resid 1: register budgets x residency caps of the R >= 3 body, and the XOR stream probe at each cap
 int g_lds = 0;          // --lds 1: the LDS nibble-table engine (production form and lab forms) beside the v_perm production;
                         // --lds 2: both engines at 3 workgroups per CU under dynamic LDS allocations of several sizes
 
@@ -272,6 +419,7 @@ struct Variant {
   int blocks_per_cu;  // 0: uncapped
   unsigned lds = 0;   // > 0: this dynamic LDS allocation instead of the blocks_per_cu rule
   int cols = 0;       // > 0: columns per workgroup when it is not bs (VEC > 1 forms)
+  bool probe = false; // a stream probe: its output is not the coding result
 };
 
 // builds the production 3-bit-slice tables (dispatch_w8.hip build_tables)
@@ -326,6 +474,7 @@ int main(int argc, char** argv) {
     else if (f == "--early0") g_early0 = std::atoi(argv[i + 1]) != 0;
     else if (f == "--vec2") g_vec2 = std::atoi(argv[i + 1]) != 0;
     else if (f == "--dense") g_dense = std::atoi(argv[i + 1]) != 0;
+    else if (f == "--resid") g_resid = std::atoi(argv[i + 1]);
     else if (f == "--lds") g_lds = std::atoi(argv[i + 1]);
     else if (f == "--sync") g_sync = std::atoi(argv[i + 1]);
     else if (f == "--sched") g_sched = std::atoi(argv[i + 1]);
@@ -435,7 +584,43 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
   const void* const ldsk = reinterpret_cast<const void*>(&gf_apply_lds<k, m>);
   const int cap = k + m <= 9 ? 4 : 3;  // dispatch_w8.hip residency_lds_bytes
   const unsigned lds_cap = ((unsigned(163840 / cap) & ~511u) - 128u * k - 4096u) & ~4095u;
-  std::vector<Variant> vs = g_sched == 2 ? std::vector<Variant>{  // the R = 1 levers (lost parity)
+  auto resid_set = [&](auto unit_tag) {
+    constexpr int X = decltype(unit_tag)::value;
+    const void* const par = reinterpret_cast<const void*>(&lab::enc_bs<k, m, X, 256>);  // the body before the sequential form
+    const void* const par3 = reinterpret_cast<const void*>(&lab::enc_par<k, m, X, 3>);
+    const void* const seq = reinterpret_cast<const void*>(&lab::enc_seq0<k, m, X>);
+    const void* const seq4 = reinterpret_cast<const void*>(&lab::enc_seq<k, m, X, 4>);
+    const void* const xr = reinterpret_cast<const void*>(&lab::xor_mix<k, m>);
+    const void* const seq3 = reinterpret_cast<const void*>(&lab::enc_seq<k, m, X, 3>);
+    const void* const w4 = reinterpret_cast<const void*>(&lab::enc_win<k, m, X, 4>);
+    const void* const w6 = reinterpret_cast<const void*>(&lab::enc_win<k, m, X, 6>);
+    const void* const w8 = reinterpret_cast<const void*>(&lab::enc_win<k, m, X, 8>);
+    const void* const wall = reinterpret_cast<const void*>(&lab::enc_win<k, m, X, 16>);
+    if (g_resid == 2)  // load windows at the caps the first sweep left standing
+      return std::vector<Variant>{
+          V{"byref_cap3", par, 256, 3},      V{"seq_cap3", seq, 256, 3},       V{"seq_w4_cap3", seq4, 256, 3},
+          V{"seq_w3_cap3", seq3, 256, 3},    V{"win4_cap3", w4, 256, 3},       V{"win6_cap3", w6, 256, 3},
+          V{"win8_cap3", w8, 256, 3},        V{"winall_cap3", wall, 256, 3},   V{"win6_cap2", w6, 256, 2},
+          V{"win8_cap2", w8, 256, 2},        V{"winall_cap2", wall, 256, 2},   V{"win4_cap4", w4, 256, 4},
+          V{"win8_cap4", w8, 256, 4},        V{"winall_cap4", wall, 256, 4},   V{"seq_cap4", seq, 256, 4},
+          V{"prod_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, X, 1, 3, 3>), 256, 3},
+      };
+    return std::vector<Variant>{
+        V{"byref_uncapped", par, 256, 0},        V{"byref_cap2", par, 256, 2},
+        V{"byref_cap3", par, 256, 3},            V{"byref_cap4", par, 256, 4},
+        V{"par_w3_uncapped", par3, 256, 0},      V{"par_w3_cap2", par3, 256, 2},
+        V{"seq_uncapped", seq, 256, 0},          V{"seq_cap2", seq, 256, 2},
+        V{"seq_cap3", seq, 256, 3},              V{"seq_cap4", seq, 256, 4},
+        V{"seq_cap5", seq, 256, 5},              V{"seq_cap6", seq, 256, 6},
+        V{"seq_w4_uncapped", seq4, 256, 0},      V{"seq_w4_cap3", seq4, 256, 3},
+        V{"seq_w4_cap4", seq4, 256, 4},
+        V{"xor_uncapped", xr, 256, 0, 0, 0, true}, V{"xor_cap2", xr, 256, 2, 0, 0, true},
+        V{"xor_cap3", xr, 256, 3, 0, 0, true},     V{"xor_cap4", xr, 256, 4, 0, 0, true},
+    };
+  };
+  std::vector<Variant> vs = g_resid ? (g_dense ? resid_set(std::integral_constant<int, N>{})
+                                               : resid_set(std::integral_constant<int, U>{}))
+                            : g_sched == 2 ? std::vector<Variant>{  // the R = 1 levers (lost parity)
       V{"prod", vperm, 256, cap},
       V{"vec2_cap2", reinterpret_cast<const void*>(&gf_apply<k, m, U, 2, 3, 3>), 256, 2, 0, 512},
       V{"vec2_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, U, 2, 3, 3>), 256, 3, 0, 512},
@@ -522,6 +707,8 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
     }
     const int per = v.cols > 0 ? v.cols : v.bs;
     const dim3 grid(unsigned((a.nvec + per - 1) / per), unsigned(stripes));
+    // more than the default 64 KiB per launch (2 per CU = 80 KiB): raise the function's limit
+    if (lds_of(v) > 65536u) CK(hipFuncSetAttribute(v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_of(v))));
     CK(hipLaunchKernel(v.fn, grid, dim3(unsigned(v.bs)), kargs, lds_of(v), nullptr));
   };
   // reference: the production launch; spot-check it against the host
@@ -555,6 +742,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
       CK(hipMemcpy(ref.back().data(), hd[size_t(s * m + r)], S, hipMemcpyDeviceToHost));
     }
   for (size_t v = 1; v < vs.size(); ++v) {
+    if (vs[v].probe) continue;
     for (int s : {0, stripes - 1})
       for (int r = 0; r < m; ++r) CK(hipMemset(hd[size_t(s * m + r)], 0, S));
     launch(vs[v]);
@@ -590,10 +778,12 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
   for (size_t v = 0; v < vs.size(); ++v) {
     std::sort(t[v].begin(), t[v].end());
     const double med = t[v][t[v].size() / 2];
-    std::printf("{\"variant\": \"%s\", \"block\": %d, \"blocks_per_cu\": %d, \"dyn_lds\": %u, \"stripes\": %d, \"median_us\": %.1f, "
-                "\"min_us\": %.1f, \"GBps\": %.0f, \"frac\": %.4f}\n",
-                vs[v].name.c_str(), vs[v].bs, vs[v].blocks_per_cu, lds_of(vs[v]), stripes, med, double(t[v][0]),
-                bytes / med / 1e3, bytes / med / 1e3 / 8000.0);
+    hipFuncAttributes fa{};
+    CK(hipFuncGetAttributes(&fa, vs[v].fn));
+    std::printf("{\"k\": %d, \"m\": %d, \"dense\": %d, \"variant\": \"%s\", \"block\": %d, \"blocks_per_cu\": %d, \"dyn_lds\": %u, "
+                "\"vgprs\": %d, \"stripes\": %d, \"median_us\": %.1f, \"min_us\": %.1f, \"GBps\": %.0f, \"frac\": %.4f}\n",
+                k, m, int(g_dense), vs[v].name.c_str(), vs[v].bs, vs[v].blocks_per_cu, lds_of(vs[v]), fa.numRegs, stripes, med,
+                double(t[v][0]), bytes / med / 1e3, bytes / med / 1e3 / 8000.0);
   }
   return 0;
 }
