@@ -11,22 +11,25 @@ Produces, under erasure_coding_test_amd/lib/:
 and the test-only checker under oracle/ (make -C oracle).
 
 An object is rebuilt when its key changes: a SHA-256 of its compiler command
-line and the bytes of its source and every header (stored beside it as
-<object>.key), so neither a touched-but-unchanged file nor a stale object with
-a newer mtime decides.  The library carries content IDs (ecgpu_build_id):
+line and the bytes of its source and of every header it includes, directly or
+not (include_closure; stored beside it as <object>.key), so neither a
+touched-but-unchanged file nor a stale object with a newer mtime decides.  The
+library carries content IDs (ecgpu_build_id):
   0  the whole library: every source and header under csrc/ + ecgpu.h + flags
      + both compilers' --version
-  1  the w = 8 kernels and their dispatch (gf_kernels_w8.hpp, gf_spec.*,
-     dispatch_w8.hip and the defaults of the knobs it reads) + HIP flags +
+  1  the w = 8 kernels and their dispatch (gf_device.hpp, gf_kernels_w8.hpp,
+     gf_spec.*, dispatch_w8.hip and the defaults of the knobs it reads) + HIP flags +
      hipcc --version -- the identity a rocprofv3 PMC record of the bench's
      launches is valid for (profiles/summarize.py writes it, bench.py checks it)
   2  the same for the w = 16 / 32 kernels, 3 for the GF(2) packet kernels,
-     4 for the scrub kernels.
+     4 for the scrub kernels; each is its own kernel header and units plus
+     the shared device vocabulary gf_device.hpp, and no other family's kernels.
 """
 from __future__ import annotations
 
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -51,9 +54,6 @@ HIP_UNITS = [(f, f + ".o", []) for f in ("ecgpu_runtime.hip", "plans.hip", "devi
                                            "pipeline.hip", "packets.hip", "scrub.hip")] + [
     (f"{t}.hip", f"{t}_r{r}.hip.o", [f"-DECGPU_SPEC_R={r}"]) for t in ("gf_spec", "wide_spec", "scrub_spec")
     for r in (1, 2, 3, 4)]
-HDRS = ["buffer_contract.hpp", "cpu_fallback.hpp", "cpu_exec.hpp", "gf_host.hpp", "knobs.hpp", "shard_stride.hpp", "host_sync.hpp", "matrix_host.hpp", "planner.hpp", "schedule_host.hpp", "gf_kernels.hpp", "gf_kernels_w8.hpp", "gf_kernels_wide.hpp",
-        "gf_kernels_packets.hpp", "gf_spec.hpp", "wide_spec.hpp", "diag_kernels_w8.hpp",
-        "runtime.hpp", "scrub_kernels.hpp", "scrub_spec.hpp"]
 DROPIN_SRCS = ["jerasure_dropin.cpp", "jerasure_surface.cpp"]
 
 CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter", f"-I{INCLUDE}", f"-I{CSRC}"]
@@ -84,15 +84,16 @@ def _run_parallel(cmds):
 # records are keyed to, unchanged.  The synchronous calls' staging
 # (ecgpu_runtime.hip), the units under it (plans.hip, devices.hip,
 # contexts.hip, host_memory.hip) and the measurement-only kernels
-# (diag_kernels*) are in no family.
+# (diag_kernels*) are in no family.  Every family has the device vocabulary
+# (gf_device.hpp) and its own kernel header, never another family's.
 KERNEL_FAMILIES = {
-    "kernels": (["gf_kernels_w8.hpp", "gf_spec.hip", "gf_spec.hpp", "dispatch_w8.hip"],
+    "kernels": (["gf_device.hpp", "gf_kernels_w8.hpp", "gf_spec.hip", "gf_spec.hpp", "dispatch_w8.hip"],
                 ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_KERNEL", "ECGPU_NT"]),
-    "wide": (["gf_kernels_w8.hpp", "gf_kernels_wide.hpp", "wide_spec.hip", "wide_spec.hpp", "dispatch_wide.hip"],
+    "wide": (["gf_device.hpp", "gf_kernels_wide.hpp", "wide_spec.hip", "wide_spec.hpp", "dispatch_wide.hip"],
              ["ECGPU_WIDE", "ECGPU_NIB16", "ECGPU_WIDE_UNITS", "ECGPU_WIDE_PIPE", "ECGPU_WIDE16_BPCU",
               "ECGPU_WIDE16_UNITS"]),
-    "packets": (["gf_kernels_w8.hpp", "gf_kernels_packets.hpp", "packets.hip"], ["ECGPU_PACKET"]),
-    "scrub": (["gf_kernels_w8.hpp", "scrub_kernels.hpp", "scrub_spec.hip", "scrub_spec.hpp", "scrub.hip"],
+    "packets": (["gf_device.hpp", "gf_kernels_packets.hpp", "packets.hip"], ["ECGPU_PACKET"]),
+    "scrub": (["gf_device.hpp", "scrub_kernels.hpp", "scrub_spec.hip", "scrub_spec.hpp", "scrub.hip"],
               ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_SCRUB_LATE"]),
 }
 
@@ -171,14 +172,32 @@ def _commit_keys():
     _pending_keys.clear()
 
 
-def _headers():
-    return [os.path.join(CSRC, h) for h in HDRS] + [os.path.join(INCLUDE, "ecgpu.h")]
+_QUOTED_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+
+
+def include_closure(src: str, dropin: bool = False) -> list:
+    """The files `src` includes with quotes, directly or not, resolved against
+    the including file's directory, csrc/, include/ and (dropin) include/dropin/
+    like the compilers' -I order; sorted paths, `src` itself not among them.
+    Angle-bracket includes -- the toolchain's, covered by its --version -- are
+    ignored."""
+    dirs = [CSRC, INCLUDE] + ([os.path.join(INCLUDE, "dropin")] if dropin else [])
+    seen, todo = set(), [os.path.abspath(src)]
+    while todo:
+        f = todo.pop()
+        with open(f) as fh:
+            names = _QUOTED_INCLUDE.findall(fh.read())
+        for n in names:
+            hit = next((p for p in (os.path.join(d, n) for d in [os.path.dirname(f)] + dirs) if os.path.exists(p)), None)
+            if hit and hit not in seen:
+                seen.add(hit)
+                todo.append(hit)
+    return sorted(seen - {os.path.abspath(src)})
 
 
 def build_native(verbose: bool = True) -> dict:
     os.makedirs(LIB, exist_ok=True)
     os.makedirs(OBJ, exist_ok=True)
-    hdrs = _headers()
     ids = build_ids()
     objs = []
     for src in HOST_SRCS:
@@ -188,14 +207,14 @@ def build_native(verbose: bool = True) -> dict:
                   f'-DECGPU_SCRUB_ID="{ids["scrub"]}"']
                  if src == "capi_host.cpp" else [])
         cmd = [CXX] + CXXFLAGS + extra + ["-fvisibility=hidden", "-c", s, "-o", o]
-        if _stale(o, [s] + hdrs, cmd):
+        if _stale(o, [s] + include_closure(s), cmd):
             _run(cmd)
         objs.append(o)
     jobs = []
     for src, obj, extra in HIP_UNITS:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, obj)
         cmd = [HIPCC] + HIPFLAGS + extra + ["-c", s, "-o", o]
-        if _stale(o, [s] + hdrs, cmd):
+        if _stale(o, [s] + include_closure(s), cmd):
             jobs.append(cmd)
         objs.append(o)
     _run_parallel(jobs)
@@ -211,8 +230,7 @@ def build_native(verbose: bool = True) -> dict:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src + ".o")
         cmd = [CXX] + CXXFLAGS + [f"-I{os.path.join(INCLUDE, 'dropin')}", "-fvisibility=hidden",
                                   "-fvisibility-inlines-hidden", "-c", s, "-o", o]
-        if _stale(o, [s] + hdrs + [os.path.join(INCLUDE, "dropin", h) for h in ("galois.h", "jerasure.h", "reed_sol.h")],
-                  cmd):
+        if _stale(o, [s] + include_closure(s, dropin=True), cmd):
             _run(cmd)
             _commit_keys()
         dropin_objs.append(o)
@@ -228,7 +246,7 @@ def build_native(verbose: bool = True) -> dict:
         s, o = os.path.join(CSRC, "diag_kernels.hip"), os.path.join(OBJ, "diag_kernels.hip.o")
         diag = os.path.join(LIB, "libecgpu_diag.so")
         cmd = [HIPCC] + HIPFLAGS + ["-c", s, "-o", o]
-        if _stale(o, [s] + hdrs, cmd):
+        if _stale(o, [s] + include_closure(s), cmd):
             _run(cmd)
             _commit_keys()
         cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", o, "-o", diag]

@@ -11,8 +11,11 @@
 //              nt bits (loads / stores)
 //   variant 15: production combine with inline-asm loads / stores carrying
 //              explicit sc0 / sc1 / nt cache bits (cache-policy probe)
-//   variant 10: production gf_apply with the round-1 2-bit-slice tables
-//              (A/B against variants 4/8, which use the 3-bit-slice ptab)
+//   variant 8: gf_apply_vec<K, R, UNITS, VEC> -- the production arithmetic
+//              with VEC in {2, 4} columns per lane (VEC 1: gf_apply itself)
+//   variant 10: gf_apply_2bit<K, R, UNITS> -- gf_apply's every-load-first
+//              form with the round-1 2-bit-slice tables (A/B against variants
+//              4/8, which use the 3-bit-slice ptab)
 //   variant 16: diag_xor_mix<K, R> -- the coding launches' exact streams (K
 //              nt loads and R nt stores of 16 B per lane, one column per
 //              lane, production grid) with no arithmetic beyond one XOR: a
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(256) void gf_apply_pol(ApplyArgs a) {
 #pragma unroll
   for (int j = 0; j < K; ++j) asm volatile("" : "+v"(x[j]));  // uses stay after the wait
   u32x4 acc[R];
-  ecgpu::dev::combine<K, R, UNITS, 3>(a, x, acc);
+  ecgpu::dev::combine<K, R, UNITS>(a, x, acc);
 #pragma unroll
   for (int r = 0; r < R; ++r) asm_store16<SP>(dp[r] + col * 16, acc[r]);
 }
@@ -235,11 +238,11 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
   } else if (variant == 8) {
     // production gf_apply with VEC columns per lane (vec in {1,2,4}); mode = UnitMask
     if (K == 10 && R == 4)
-      fn = vec == 1 ? &ecgpu::dev::gf_apply<10, 4, 3, 1>
-                    : vec == 2 ? &ecgpu::dev::gf_apply<10, 4, 3, 2> : &ecgpu::dev::gf_apply<10, 4, 3, 4>;
+      fn = vec == 1 ? &ecgpu::dev::gf_apply<10, 4, 3>
+                    : vec == 2 ? &ecgpu::dev::gf_apply_vec<10, 4, 3, 2> : &ecgpu::dev::gf_apply_vec<10, 4, 3, 4>;
     if (K == 10 && R == 1)
-      fn = vec == 1 ? &ecgpu::dev::gf_apply<10, 1, 4, 1>
-                    : vec == 2 ? &ecgpu::dev::gf_apply<10, 1, 4, 2> : &ecgpu::dev::gf_apply<10, 1, 4, 4>;
+      fn = vec == 1 ? &ecgpu::dev::gf_apply<10, 1, 4>
+                    : vec == 2 ? &ecgpu::dev::gf_apply_vec<10, 1, 4, 2> : &ecgpu::dev::gf_apply_vec<10, 1, 4, 4>;
   } else if (variant == 9) {
     // access-pattern probe: XOR-only gf_apply_perm over (K, R) shapes
     vec = 1;
@@ -255,8 +258,8 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
     if (K == 2 && R == 1) fn = &ecgpu::dev::gf_apply_perm<2, 1, 1, 3>;
   } else if (variant == 10) {
     vec = 1;
-    if (K == 10 && R == 4) fn = &ecgpu::dev::gf_apply<10, 4, 3, 1, 2>;
-    if (K == 10 && R == 1) fn = mode == 4 ? &ecgpu::dev::gf_apply<10, 1, 4, 1, 2> : &ecgpu::dev::gf_apply<10, 1, 0, 1, 2>;
+    if (K == 10 && R == 4) fn = &ecgpu::dev::gf_apply_2bit<10, 4, 3>;
+    if (K == 10 && R == 1) fn = mode == 4 ? &ecgpu::dev::gf_apply_2bit<10, 1, 4> : &ecgpu::dev::gf_apply_2bit<10, 1, 0>;
   } else if (variant == 11) {
     vec = 1;
     if (K == 1) fn = nt ? &diag_read_regs<1, 1> : &diag_read_regs<1, 0>;
@@ -270,10 +273,10 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
     const int ntb = vec;
     vec = 1;
 #define ECGPU_PICK(KK, RR, UU)                                                                              \
-  (variant == 13 ? (ntb == 0 ? &gf_apply<KK, RR, UU, 1, 3, 0> : ntb == 1 ? &gf_apply<KK, RR, UU, 1, 3, 1>   \
-                    : ntb == 2 ? &gf_apply<KK, RR, UU, 1, 3, 2> : &gf_apply<KK, RR, UU, 1, 3, 3>)           \
-                 : (ntb == 0 ? &gf_apply_dma<KK, RR, UU, 3, 0> : ntb == 1 ? &gf_apply_dma<KK, RR, UU, 3, 1> \
-                    : ntb == 2 ? &gf_apply_dma<KK, RR, UU, 3, 2> : &gf_apply_dma<KK, RR, UU, 3, 3>))
+  (variant == 13 ? (ntb == 0 ? &gf_apply<KK, RR, UU, 0> : ntb == 1 ? &gf_apply<KK, RR, UU, 1>         \
+                    : ntb == 2 ? &gf_apply<KK, RR, UU, 2> : &gf_apply<KK, RR, UU, 3>)                 \
+                 : (ntb == 0 ? &gf_apply_dma<KK, RR, UU, 0> : ntb == 1 ? &gf_apply_dma<KK, RR, UU, 1> \
+                    : ntb == 2 ? &gf_apply_dma<KK, RR, UU, 2> : &gf_apply_dma<KK, RR, UU, 3>))
     if (K == 10 && R == 4) fn = mode == 0 ? ECGPU_PICK(10, 4, 0) : ECGPU_PICK(10, 4, 3);
     if (K == 10 && R == 1) fn = mode == 4 ? ECGPU_PICK(10, 1, 4) : ECGPU_PICK(10, 1, 0);
     if (K == 6 && R == 3) fn = ECGPU_PICK(6, 3, 3);

@@ -3,7 +3,8 @@
 // here leaves the production kernels' build ID -- and the PMC records keyed to
 // it -- unchanged (erasure_coding_test_amd/build.py).  Each was measured
 // against the production gf_apply and not kept: the round-1
-// 2-bit PERM form with its coefficient-class modes, LDS-DMA loads, an
+// 2-bit PERM form with its coefficient-class modes, the production combine
+// with VEC columns per lane or with the 2-bit-slice tables, LDS-DMA loads, an
 // occupancy-8 register budget, a persistent streaming form; plus the copy
 // kernel behind the bench's copy ceiling.
 #pragma once
@@ -11,6 +12,34 @@
 
 namespace ecgpu {
 namespace dev {
+
+// Cache policy chosen at run time (ApplyArgs::nt).  Called with a literal, or
+// under a branch on a.nt that duplicates the loop: a `nt ? a : b` pair of
+// accesses is merged into one plain access (gf_device.hpp load16t).
+__device__ __forceinline__ u32x4 load16(const uint8_t* p, int64_t col, int nt) {
+  const gu32x4* a = (const gu32x4*)p + col;  // C cast: generic -> global address space
+  return nt ? __builtin_nontemporal_load(a) : *a;
+}
+
+__device__ __forceinline__ void store16(uint8_t* p, int64_t col, const u32x4& v, int nt) {
+  gu32x4* a = (gu32x4*)p + col;
+  if (nt)
+    __builtin_nontemporal_store(v, a);
+  else
+    *a = v;
+}
+
+// acc ^ c*x for one dword from the coefficient's 2-bit-slice table q.
+__device__ __forceinline__ uint32_t mac_word(uint32_t acc, const u32x4& q, uint32_t x) {
+  const uint32_t s0 = x & kLo2, s1 = (x >> 2) & kLo2, s2 = (x >> 4) & kLo2, s3 = (x >> 6) & kLo2;
+  return xor3(acc, xor3(perm_lookup(q.x, s0), perm_lookup(q.y, s1), perm_lookup(q.z, s2)), perm_lookup(q.w, s3));
+}
+
+// c*x for one dword, from the coefficient's 3-bit-slice table t and x's selectors.
+__device__ __forceinline__ uint32_t mul3(const uint32_t* __restrict__ t, const Sel3& s) {
+  return xor3(__builtin_amdgcn_perm(t[1], t[0], s.s0), __builtin_amdgcn_perm(t[3], t[2], s.s1),
+              __builtin_amdgcn_perm(t[4], t[4], s.s2));
+}
 
 // How a launch treats coefficients 0 and 1.
 enum CoefMode : int {
@@ -119,12 +148,114 @@ __global__ __launch_bounds__(kBlock) void gf_apply_perm(ApplyArgs a) {
   }
 }
 
+// The production arithmetic (3-bit-slice tables, compile-time unit structure)
+// with VEC columns per lane: lane l of block b handles the 16-byte columns
+// (b*VEC + v)*256 + l, v < VEC, of every shard of stripe blockIdx.y; all
+// K*VEC loads are issued before any arithmetic, then R*VEC stores.  Cache
+// policy: a.nt.  Unlike gf_apply it does not read a.stripe_fast (as a branch
+// of gf_apply_body this form did; no launch of it ever set the field).
+template <int K, int R, int UNITS, int VEC>
+__global__ __launch_bounds__(kBlock) void gf_apply_vec(ApplyArgs a) {
+  const int64_t col0 = int64_t(blockIdx.x) * (VEC * kBlock) + threadIdx.x;
+  if (col0 >= a.nvec) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* dp[R];  // all pointers before the first store (see gf_apply_body)
+#pragma unroll
+  for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
+
+  bool live[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) live[v] = col0 + v * kBlock < a.nvec;
+  u32x4 x[VEC][K];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    if (!live[v]) continue;
+    if (a.nt) {
+#pragma unroll
+      for (int j = 0; j < K; ++j) x[v][j] = load16(sp[j], col0 + v * kBlock, 1);
+    } else {
+#pragma unroll
+      for (int j = 0; j < K; ++j) x[v][j] = load16(sp[j], col0 + v * kBlock, 0);
+    }
+  }
+
+  u32x4 acc[VEC][R];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v)
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[v][r] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (is_unit<UNITS>(r, j)) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v][r] ^= x[v][j];
+      } else {
+        const uint32_t* t = a.ptab + (r * K + j) * kP3Words;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) acc[v][r][c] ^= mul3(t, sel3(x[v][j][c]));
+      }
+    }
+  }
+
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) {
+    if (!live[v]) continue;
+    if (a.nt) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) store16(dp[r], col0 + v * kBlock, acc[v][r], 1);
+    } else {
+#pragma unroll
+      for (int r = 0; r < R; ++r) store16(dp[r], col0 + v * kBlock, acc[v][r], 0);
+    }
+  }
+}
+
+// gf_apply's one-column, every-load-first form with the round-1 2-bit-slice
+// tables (qtab) in place of the 3-bit-slice ones; non-temporal loads and
+// stores.  Does not read a.stripe_fast either (see gf_apply_vec).
+template <int K, int R, int UNITS>
+__global__ __launch_bounds__(kBlock) void gf_apply_2bit(ApplyArgs a) {
+  const int64_t col = int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (col >= a.nvec) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* dp[R];  // all pointers before the first store (see gf_apply_body)
+#pragma unroll
+  for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
+  u32x4 x[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) x[j] = load16t<1>(sp[j], col);
+  u32x4 acc[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (is_unit<UNITS>(r, j)) {
+        acc[r] ^= x[j];
+      } else {
+        const u32x4 q = a.qtab[r * K + j];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[r][c] = mac_word(acc[r][c], q, x[j][c]);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < R; ++r) store16t<1>(dp[r], col, acc[r]);
+}
+
 // LDS-DMA form: the K source columns of a lane arrive by
 // global_load_lds_dwordx4 (one 1 KiB piece per wave-instruction, written to
 // LDS at wave base + lane*16, no VGPR destination) instead of register
 // loads; the lane reads back only its own 16 B, so no barrier is needed,
 // just the wait on the VM counter.  K KiB of LDS per wave.
-template <int K, int R, int UNITS, int SLICES = 3, int NT = 3>
+template <int K, int R, int UNITS, int NT = 3>
 __global__ __launch_bounds__(kBlock) void gf_apply_dma(ApplyArgs a) {
   __shared__ __attribute__((aligned(16))) u32x4 stage[kBlock / 64][K][64];
   const int s = blockIdx.y;
@@ -149,13 +280,13 @@ __global__ __launch_bounds__(kBlock) void gf_apply_dma(ApplyArgs a) {
   u32x4 x[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) x[j] = stage[w][j][lane];
-  combine_store<K, R, UNITS, SLICES, (NT >> 1)>(a, x, dp, col);
+  combine_store<K, R, UNITS, (NT >> 1)>(a, x, dp, col);
 }
 
 // Same body, register budget capped for 8 waves/SIMD (<= 64 VGPRs).
 template <int K, int R, int UNITS>
 __global__ __launch_bounds__(kBlock, 8) void gf_apply_occ8(ApplyArgs a) {
-  gf_apply_body<K, R, UNITS, 1>(a);
+  gf_apply_body<K, R, UNITS>(a);
 }
 
 // ------------------------------------------------------ PERM, streaming ----

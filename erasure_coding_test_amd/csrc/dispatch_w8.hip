@@ -1,7 +1,8 @@
 // dispatch_w8.hip -- how a w = 8 plan launches: the production v_perm engine
 // or the LDS nibble-table engine (gf_kernels_w8.hpp, specialised in
 // gf_spec.hip), the unit-coefficient structure of each launch, its residency
-// cap and store policy, the coefficient tables a plan uploads.  With
+// cap and store policy, the coefficient tables a plan uploads, and the
+// byte-tail kernel gf_apply_bytes.  With gf_device.hpp,
 // gf_kernels_w8.hpp and gf_spec.* this file is the w = 8 kernel build ID
 // (ecgpu_build_id(1), erasure_coding_test_amd/build.py): what a rocprofv3 PMC
 // record of the bench's encode / decode launches is valid for.  The
@@ -20,7 +21,7 @@
 
 #include "ecgpu.h"
 #include "gf_host.hpp"
-#include "gf_kernels.hpp"
+#include "gf_kernels_w8.hpp"
 #include "knobs.hpp"
 #include "runtime.hpp"
 #include "gf_spec.hpp"
@@ -29,6 +30,29 @@ using namespace ecgpu;
 using namespace ecgpu::rt;
 using dev::ApplyArgs;
 using dev::u32x4;
+
+namespace ecgpu {
+namespace dev {
+
+// --------------------------------------- bytes: tails, misaligned shards ----
+// One lane per byte in [byte0, size); any K, R <= kMaxRows, any alignment.
+static __global__ __launch_bounds__(kBlock) void gf_apply_bytes(ApplyArgs a) {
+  const int64_t x = a.byte0 + int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (x >= a.size) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
+  uint8_t* const* dp = a.dst + int64_t(s) * a.dst_stride + a.row0;
+  uint32_t acc[kMaxRows] = {0u, 0u, 0u, 0u};
+  for (int j = 0; j < a.K; ++j) {
+    const uint32_t v = sp[j][x];
+    const uint32_t s0 = v & 3u, s1 = (v >> 2) & 3u, s2 = (v >> 4) & 3u, s3 = v >> 6;
+    for (int r = 0; r < a.R; ++r) acc[r] ^= gf_mul_perm(a.qtab[r * a.K + j], s0, s1, s2, s3);
+  }
+  for (int r = 0; r < a.R; ++r) dp[r][x] = uint8_t(acc[r]);
+}
+
+}  // namespace dev
+}  // namespace ecgpu
 
 ECGPU_RT_BEGIN
 
@@ -128,7 +152,7 @@ bool cap_for(int K, int R, int mul_terms, bool seq) {
 
 // Per-coefficient tables.  PERM: word p holds c*(e << 2p) in byte e.  LDS:
 // 16 low-nibble products then 16 high-nibble products.
-// P3 (production, gf_kernels.hpp mul3): T0[e] = c*e and T1[e] = c*(e << 3)
+// P3 (production, gf_device.hpp mac3): T0[e] = c*e and T1[e] = c*(e << 3)
 // for e < 8 as dword pairs (low dword = entries 0..3), T2[e] = c*(e << 6).
 void build_tables(int c, u32x4* q, uint32_t* p3, uint8_t* nib) {
   const auto& T = gf8().mul[c & 0xFF];
@@ -187,7 +211,6 @@ int plan_launch(ecgpu_plan* p, hipStream_t stream) {
   const int64_t nvec = p->aligned ? p->size / 16 : 0;
   const int64_t byte0 = nvec * 16;
   const dim3 block(dev::kBlock);
-  constexpr int kMaxGridY = 65535;
   for (int r0 = 0; r0 < p->rows; r0 += dev::kMaxRows) {
     const int R = std::min(dev::kMaxRows, p->rows - r0);
     const bool spec = K <= dev::kMaxSpecK;
@@ -215,8 +238,8 @@ int plan_launch(ecgpu_plan* p, hipStream_t stream) {
           if (c == 1) unit |= uint64_t(1) << (r * K + j);
           if (c == 0) zero |= uint64_t(1) << (r * K + j);
         }
-    for (int s0 = 0; s0 < p->stripes; s0 += kMaxGridY) {
-      const int ns = std::min(kMaxGridY, p->stripes - s0);
+    for (int s0 = 0; s0 < p->stripes; s0 += dev::kMaxGridY) {
+      const int ns = std::min(dev::kMaxGridY, p->stripes - s0);
       ApplyArgs a{};
       a.qtab = p->d_q + size_t(r0) * K;
       a.ptab = p->d_p3 + size_t(r0) * K * dev::kP3Words;

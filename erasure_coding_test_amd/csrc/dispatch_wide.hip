@@ -16,7 +16,7 @@
 
 #include "ecgpu.h"
 #include "gf_host.hpp"
-#include "gf_kernels.hpp"
+#include "gf_kernels_wide.hpp"
 #include "knobs.hpp"
 #include "runtime.hpp"
 #include "wide_spec.hpp"
@@ -138,7 +138,6 @@ int plan_launch_wide(ecgpu_plan* p, hipStream_t stream) {
   const int64_t nvec = p->aligned ? p->size / 16 : 0;
   const int64_t byte0 = nvec * 16;
   const dim3 block(dev::kBlock);
-  constexpr int kMaxGridY = 65535;
   const bool force_perm = knob(Knob::kWidePerm) == 1;
   for (int r0 = 0; r0 < p->rows; r0 += dev::kMaxRows) {
     const int R = std::min(dev::kMaxRows, p->rows - r0);
@@ -210,8 +209,8 @@ int plan_launch_wide(ecgpu_plan* p, hipStream_t stream) {
       }
     const unsigned launch_lds =
         piped && pack16 && unit_rc ? unsigned(K) * unsigned(dev::nib16_source_bytes(R)) : nib_lds;
-    for (int s0 = 0; s0 < p->stripes; s0 += kMaxGridY) {
-      const int ns = std::min(kMaxGridY, p->stripes - s0);
+    for (int s0 = 0; s0 < p->stripes; s0 += dev::kMaxGridY) {
+      const int ns = std::min(dev::kMaxGridY, p->stripes - s0);
       ApplyArgs a{};
       a.wtab = nib ? p->d_wnib + size_t(r0) * K * dev::kNibWords : p->d_w + size_t(r0) * K * nw;
       a.wcls = p->d_wcls + size_t(r0) * K;

@@ -35,7 +35,6 @@
 #include "cpu_fallback.hpp"
 #include "ecgpu.h"
 #include "gf_host.hpp"
-#include "gf_kernels.hpp"
 #include "gf_spec.hpp"
 #include "knobs.hpp"
 #include "planner.hpp"

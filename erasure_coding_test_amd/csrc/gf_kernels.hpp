@@ -28,9 +28,22 @@
 // gf_apply_perm (2-bit slices, runtime coefficient classes) and the LDS-DMA
 // form are kept for the A/B probes of the diagnostic library.
 //
-// The kernels live in three headers: gf_kernels_w8.hpp (shared vocabulary and
-// every w = 8 kernel), gf_kernels_wide.hpp (w = 16 / 32), gf_kernels_packets.hpp
-// (GF(2) packet coding).
+// The headers come in three layers:
+//  1. gf_device.hpp -- the vocabulary every family uses (argument blocks,
+//     constants, cache-policy loads / stores, the v_perm / XOR3 helpers); no
+//     __global__, so the host-side units that need only the argument and
+//     kernel-pointer types (runtime.hpp, *_spec.hpp) compile no kernel.
+//  2. The production kernels, one header per family, each included only by
+//     the units that instantiate its kernels or take their address:
+//     gf_kernels_w8.hpp (gf_spec.hip, dispatch_w8.hip), gf_kernels_wide.hpp
+//     (wide_spec.hip, dispatch_wide.hip), gf_kernels_packets.hpp
+//     (packets.hip), scrub_kernels.hpp (scrub_spec.hip, scrub.hip).  The
+//     non-template kernels are compiled once, in the unit that launches them
+//     (gf_apply_bytes in dispatch_w8.hip, the scrub byte kernels in scrub.hip).
+//  3. diag_kernels_w8.hpp -- measurement-only forms, libecgpu_diag.so and
+//     tools/ only.
+// This header is the umbrella for the tools, the diagnostic library and the
+// resource tests; no unit of libecgpu.so includes it.
 #pragma once
 #include "gf_kernels_w8.hpp"
 #include "gf_kernels_wide.hpp"

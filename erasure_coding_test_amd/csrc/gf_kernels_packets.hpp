@@ -1,7 +1,10 @@
 // gf_kernels_packets.hpp -- GF(2) bit-matrix / schedule coding over packet rows
-// (jerasure_bitmatrix_* / jerasure_schedule_*).  Included through gf_kernels.hpp.
+// (jerasure_bitmatrix_* / jerasure_schedule_*), on the device vocabulary of
+// gf_device.hpp.  Included by packets.hip alone in the library (it holds the
+// non-template gf_xor_packets_bytes), and through gf_kernels.hpp (the
+// overview) by the tools and the diagnostic library.
 #pragma once
-#include "gf_kernels_w8.hpp"
+#include "gf_device.hpp"
 
 namespace ecgpu {
 namespace dev {

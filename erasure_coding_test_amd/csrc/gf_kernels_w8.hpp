@@ -1,249 +1,34 @@
-// gf_kernels_w8.hpp -- the shared kernel vocabulary (argument blocks, cache-policy
-// loads / stores, constant-address table reads) and the w = 8 kernels of the
-// library: the production v_perm engine gf_apply, the one-stripe inline form,
-// the LDS nibble-table engine, the generic-K and byte-tail kernels.  Included
-// through gf_kernels.hpp (the overview).  The measurement-only forms (2-bit
-// PERM, LDS-DMA, occupancy-8, streaming, copy) live in diag_kernels_w8.hpp,
-// compiled into libecgpu_diag.so only.
+// gf_kernels_w8.hpp -- the production w = 8 kernels of the library: the
+// v_perm engine gf_apply, the one-stripe inline form, the LDS nibble-table
+// engine and the generic-K kernel, on the device vocabulary of gf_device.hpp.
+// Included by the units that instantiate them (gf_spec.hip, dispatch_w8.hip,
+// which also holds the byte-tail kernel) and through gf_kernels.hpp (the
+// overview) by the tools.  The measurement-only forms (VEC columns per lane,
+// 2-bit PERM, LDS-DMA, occupancy-8, streaming, copy) live in
+// diag_kernels_w8.hpp, compiled into libecgpu_diag.so only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gf_device.hpp"
+
 namespace ecgpu {
 namespace dev {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kBlock = 256;              // 4 waves
-constexpr int kMaxRows = 4;              // rows per launch
-constexpr int kMaxSpecK = 16;            // K specialised at compile time
-constexpr uint32_t kQ0Unit = 0x03020100u;  // PERM table word 0 of coefficient 1
-constexpr uint32_t kLo2 = 0x03030303u;
-
-struct ApplyArgs {
-  const u32x4* qtab;              // [R][K] PERM tables (16 B each)
-  const uint32_t* ptab;           // [R][K][kP3Words] 3-bit-slice PERM tables (production kernel)
-  const uint8_t* ntab;            // [R][K][32] nibble tables (LDS engine)
-  const uint8_t* const* src;      // [stripes][src_stride] device pointers
-  uint8_t* const* dst;            // [stripes][dst_stride] device pointers
-  int64_t nvec;                   // 16-B columns per shard in the vector part
-  int64_t size;                   // bytes per shard
-  int64_t byte0;                  // first byte handled by the byte kernel
-  uint64_t unit_mask;             // bit r*K+j: coefficient == 1 (this launch's rows)
-  uint64_t zero_mask;             // bit r*K+j: coefficient == 0
-  int src_stride, dst_stride, row0;  // row0 = first dst column of this launch
-  int K, R;                       // runtime copies (generic / byte kernels)
-  int nt;                         // 1: non-temporal loads/stores
-  int stripe_fast;                // 1: blockIdx.x = stripe, blockIdx.y = column block
-  const uint32_t* wtab;           // [R][K][2 * Wide<W>::kPerms] wide-word tables (w = 16 / 32)
-  const uint8_t* wcls;            // [R][K] wide coefficient class: 0 general, 1 unit, 2 zero
-};
-
-__device__ __forceinline__ uint32_t perm_lookup(uint32_t table, uint32_t sel) {
-  // v_perm_b32: selector bytes 0..3 pick bytes of the second operand.
-  return __builtin_amdgcn_perm(table, table, sel);
-}
-
-__device__ __forceinline__ uint32_t gf_mul_perm(const u32x4& q, uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3) {
-  return perm_lookup(q.x, s0) ^ perm_lookup(q.y, s1) ^ perm_lookup(q.z, s2) ^ perm_lookup(q.w, s3);
-}
-
-// Shards live in global memory: address space 1 makes these global_load /
-// global_store (not flat_*, which also arbitrates the LDS aperture).
-typedef __attribute__((address_space(1))) u32x4 gu32x4;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) u32x2 gu32x2;
-
-__device__ __forceinline__ u32x4 load16(const uint8_t* p, int64_t col, int nt) {
-  const gu32x4* a = (const gu32x4*)p + col;  // C cast: generic -> global address space
-  return nt ? __builtin_nontemporal_load(a) : *a;
-}
-
-// Compile-time cache policy.  A runtime `nt ? nontemporal : plain` pair is
-// merged by the compiler into ONE plain access (the two loads differ only in
-// metadata), so the production kernels take the policy as a template
-// argument: NT = 1 emits the `nt` bit on the global_load / global_store.
-template <int NT>
-__device__ __forceinline__ u32x4 load16t(const uint8_t* p, int64_t col) {
-  const gu32x4* a = (const gu32x4*)p + col;
-  if constexpr (NT != 0) return __builtin_nontemporal_load(a);
-  else return *a;
-}
-
-// A kernel-invariant table entry (pointer tables, row masks) read through the
-// constant address space: always a scalar load.  A generic load issued after
-// the kernel's own vector stores must be a VECTOR load (the scalar cache is
-// not coherent with vector stores), and waiting for it (vmcnt(0)) waits for
-// every shard load issued before it -- in a column loop that serialised the
-// K source loads of each iteration.  Valid because no table is written while
-// a kernel runs.
-template <class T>
-__device__ __forceinline__ T kload(const T* p, int64_t i) {
-  typedef __attribute__((address_space(4))) const T kT;
-  return ((const kT*)p)[i];  // C cast: generic -> constant
-}
-
-// Store cache policy POL: 0 plain, 1 non-temporal (`nt`).  (Stores that
-// bypass the XCD's L2 -- `sc1`, `sc0 sc1`, inline asm -- were probed in round
-// 1 and were equal or slower in the bench's back-to-back launches, DESIGN.md
-// §5; they live only in the diagnostic library.)
-template <int POL>
-__device__ __forceinline__ void store16t(uint8_t* p, int64_t col, const u32x4& v) {
-  gu32x4* a = (gu32x4*)p + col;
-  if constexpr (POL == 1) {
-    __builtin_nontemporal_store(v, a);
-  } else {
-    *a = v;
-  }
-}
-
-__device__ __forceinline__ void store16(uint8_t* p, int64_t col, const u32x4& v, int nt) {
-  gu32x4* a = (gu32x4*)p + col;
-  if (nt)
-    __builtin_nontemporal_store(v, a);
-  else
-    *a = v;
-}
-
-typedef __attribute__((address_space(3))) const u32x4 lds_u32x4;
-
-// ------------------------------------------------- PERM, production ----
-// Unit-coefficient structure known at compile time (host checks it exactly):
-//   kUnitCol0 -- coefficient (r, 0) == 1 for every row of the launch
-//   kUnitRow0 -- coefficient (0, j) == 1 for every source (launch row 0)
-//   kUnitAll  -- every coefficient == 1 (pure XOR, e.g. decode of one data
-//                shard with the all-ones parity row)
-// reed_sol_vandermonde_coding_matrix always has row 0 and column 0 all ones
-// (reed_sol.cpp:324-349), so RS encode launches take kUnitCol0|kUnitRow0.
-// A unit term costs one XOR and no selectors; every other term is 4 v_perm
-// + 2 v_bitop3 (XOR3) per dword.
-enum UnitMask : int { kUnitNone = 0, kUnitCol0 = 1, kUnitRow0 = 2, kUnitAll = 4 };
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-template <int UNITS>
-__device__ __forceinline__ constexpr bool is_unit(int r, int j) {
-  return (UNITS & kUnitAll) || ((UNITS & kUnitCol0) && j == 0) || ((UNITS & kUnitRow0) && r == 0);
-}
-
-__device__ __forceinline__ uint32_t mac_word(uint32_t acc, const u32x4& q, uint32_t x) {
-  const uint32_t s0 = x & kLo2, s1 = (x >> 2) & kLo2, s2 = (x >> 4) & kLo2, s3 = (x >> 6) & kLo2;
-  return xor3(acc, xor3(perm_lookup(q.x, s0), perm_lookup(q.y, s1), perm_lookup(q.z, s2)), perm_lookup(q.w, s3));
-}
-
-// 3-bit slices (production): v_perm picks from EIGHT bytes -- the pair
-// {hi, lo} -- so a byte splits into slices [0:2], [3:5], [6:7] and
-//   c*x = T0[x & 7] ^ T1[(x >> 3) & 7] ^ T2[x >> 6],  Tp[e] = c*(e << 3p),
-// T0 and T1 each a dword pair, T2 one dword: 3 v_perm per coefficient-dword
-// instead of 4, and 5 selector ops per source dword instead of 7.  Table
-// layout per coefficient (kP3Words dwords): T0lo T0hi T1lo T1hi T2 (pad).
-constexpr int kP3Words = 8;
-constexpr uint32_t kLo3 = 0x07070707u;
-
-struct Sel3 {
-  uint32_t s0, s1, s2;
-};
-
-__device__ __forceinline__ Sel3 sel3(uint32_t x) { return Sel3{x & kLo3, (x >> 3) & kLo3, (x >> 6) & kLo2}; }
-
-// c*x for one dword, from the coefficient's table t and x's selectors.
-__device__ __forceinline__ uint32_t mul3(const uint32_t* __restrict__ t, const Sel3& s) {
-  return xor3(__builtin_amdgcn_perm(t[1], t[0], s.s0), __builtin_amdgcn_perm(t[3], t[2], s.s1),
-              __builtin_amdgcn_perm(t[4], t[4], s.s2));
-}
-
-// XOR accumulator that folds terms three at a time: v_bitop3 (XOR3) takes
-// the running value plus TWO new terms, so one odd term is parked until its
-// partner arrives.  N terms cost ceil(N/2) instead of N XORs (the compiler
-// does not reassociate the chain itself).  `has` is a compile-time constant
-// after full unrolling.
-struct Xacc {
-  uint32_t acc = 0u, pend = 0u;
-  bool has = false;
-  __device__ __forceinline__ void add(uint32_t v) {
-    if (has) {
-      acc = xor3(acc, pend, v);
-      has = false;
-    } else {
-      pend = v;
-      has = true;
-    }
-  }
-  __device__ __forceinline__ uint32_t value() const { return has ? (acc ^ pend) : acc; }
-};
-
-typedef __attribute__((address_space(4))) const uint32_t kconst_u32;
-
-__device__ __forceinline__ void mac3(Xacc& x, const kconst_u32* __restrict__ t, const Sel3& s) {
-  x.add(__builtin_amdgcn_perm(t[1], t[0], s.s0));
-  x.add(__builtin_amdgcn_perm(t[3], t[2], s.s1));
-  x.add(__builtin_amdgcn_perm(t[4], t[4], s.s2));
-}
-
-// R output columns from the K source columns of one lane with the
-// 3-bit-slice tables at `ptab` ([R][K][kP3Words], constant address space: a
-// device table or the launch's own kernel arguments, see gf_apply_inl).
+// R output columns from the K source columns of one lane with the launch's
+// 3-bit-slice tables (combine_store: then R stores).
 template <int K, int R, int UNITS>
-__device__ __forceinline__ void combine3(const kconst_u32* __restrict__ ptab, const u32x4 (&x)[K], u32x4 (&acc)[R]) {
-  Xacc xa[R][4];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    Sel3 sl[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) sl[c] = sel3(x[j][c]);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (is_unit<UNITS>(r, j)) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) xa[r][c].add(x[j][c]);
-      } else {
-        const kconst_u32* t = ptab + (r * K + j) * kP3Words;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) mac3(xa[r][c], t, sl[c]);
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[r][c] = xa[r][c].value();
-}
-
-// R output columns from the K source columns of one lane (combine_store:
-// then R stores).  SLICES = 3: production 3-bit-slice tables (ptab); 2: the round-1 2-bit
-// form (qtab), kept for A/B timing in the diagnostic library.
-template <int K, int R, int UNITS, int SLICES>
 __device__ __forceinline__ void combine(const ApplyArgs& a, const u32x4 (&x)[K], u32x4 (&acc)[R]) {
-  if constexpr (SLICES == 3) {
-    // constant address space: always a scalar load, even after an LDS-DMA
-    // (which the compiler otherwise treats as a clobber)
-    combine3<K, R, UNITS>((const kconst_u32*)a.ptab, x, acc);  // C cast: generic -> constant
-  } else {
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (is_unit<UNITS>(r, j)) {
-          acc[r] ^= x[j];
-        } else {
-          const u32x4 q = a.qtab[r * K + j];
-#pragma unroll
-          for (int c = 0; c < 4; ++c) acc[r][c] = mac_word(acc[r][c], q, x[j][c]);
-        }
-      }
-    }
-  }
+  // constant address space: always a scalar load, even after an LDS-DMA
+  // (which the compiler otherwise treats as a clobber)
+  combine3<K, R, UNITS>((const kconst_u32*)a.ptab, x, acc);  // C cast: generic -> constant
 }
 
-template <int K, int R, int UNITS, int SLICES, int NTS>
+template <int K, int R, int UNITS, int NTS>
 __device__ __forceinline__ void combine_store(const ApplyArgs& a, const u32x4 (&x)[K], uint8_t* const (&dp)[R],
                                               int64_t col) {
   u32x4 acc[R];
-  combine<K, R, UNITS, SLICES>(a, x, acc);
+  combine<K, R, UNITS>(a, x, acc);
 #pragma unroll
   for (int r = 0; r < R; ++r) store16t<NTS>(dp[r], col, acc[r]);
 }
@@ -263,16 +48,15 @@ constexpr int kSeqMinRows = 3;
 template <int K>
 constexpr int load_window() { return K <= 10 ? 6 : K; }
 
-// Lane l of block b handles the 16-byte columns (b*VEC + v)*256 + l, v < VEC,
-// of every shard of stripe s; R < kSeqMinRows and VEC > 1: all K*VEC loads
-// are issued before any arithmetic, then R*VEC stores.  NT: bit 0 =
-// non-temporal loads, NT >> 1 = store policy of store16t (VEC == 1; the
-// VEC > 1 probe form follows a.nt).
-template <int K, int R, int UNITS, int VEC, int SLICES = 3, int NT = 3>
+// Lane l of block b handles the 16-byte column b*256 + l of every shard of
+// stripe s; R < kSeqMinRows: all K loads are issued before any arithmetic,
+// then R stores.  NT: bit 0 = non-temporal loads, NT >> 1 = store policy of
+// store16t.
+template <int K, int R, int UNITS, int NT = 3>
 __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
   const unsigned cblk = a.stripe_fast ? blockIdx.y : blockIdx.x;
   const int s = a.stripe_fast ? blockIdx.x : blockIdx.y;
-  const int64_t col0 = int64_t(cblk) * (VEC * kBlock) + threadIdx.x;
+  const int64_t col0 = int64_t(cblk) * kBlock + threadIdx.x;
   if (col0 >= a.nvec) return;
   const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
   // Fetch ALL pointers before the first store: a pointer read after a store
@@ -282,7 +66,7 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
 #pragma unroll
   for (int r = 0; r < R; ++r) dp[r] = a.dst[int64_t(s) * a.dst_stride + a.row0 + r];
 
-  if constexpr (VEC == 1 && SLICES == 3 && R >= kSeqMinRows) {
+  if constexpr (R >= kSeqMinRows) {
     // Three or four output rows (production): the sources are consumed one
     // after the other, written out here in the kernel body.  The same
     // arithmetic through combine3 -- x[] and acc[] handed down by reference
@@ -329,66 +113,12 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
       for (int c = 0; c < 4; ++c) o[c] = xa[r][c].value();
       store16t<(NT >> 1)>(dp[r], col0, o);
     }
-    return;
-  } else if constexpr (VEC == 1) {
-    // Single column per lane, one or two output rows (46-58 VGPRs for the
-    // R = 1 decodes) and the 2-bit-slice diagnostic form.
+  } else {
+    // One or two output rows (46-58 VGPRs for the R = 1 decodes).
     u32x4 x[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) x[j] = load16t<NT & 1>(sp[j], col0);
-    combine_store<K, R, UNITS, SLICES, (NT >> 1)>(a, x, dp, col0);
-    return;
-  }
-
-  bool live[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) live[v] = col0 + v * kBlock < a.nvec;
-  u32x4 x[VEC][K];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    if (!live[v]) continue;
-    if (a.nt) {
-#pragma unroll
-      for (int j = 0; j < K; ++j) x[v][j] = load16(sp[j], col0 + v * kBlock, 1);
-    } else {
-#pragma unroll
-      for (int j = 0; j < K; ++j) x[v][j] = load16(sp[j], col0 + v * kBlock, 0);
-    }
-  }
-
-  u32x4 acc[VEC][R];
-#pragma unroll
-  for (int v = 0; v < VEC; ++v)
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[v][r] = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (is_unit<UNITS>(r, j)) {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[v][r] ^= x[v][j];
-      } else {
-        static_assert(SLICES == 3 || VEC == 1, "VEC > 1 uses the 3-bit-slice tables");
-        const uint32_t* t = a.ptab + (r * K + j) * kP3Words;
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) acc[v][r][c] ^= mul3(t, sel3(x[v][j][c]));
-      }
-    }
-  }
-
-#pragma unroll
-  for (int v = 0; v < VEC; ++v) {
-    if (!live[v]) continue;
-    if (a.nt) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) store16(dp[r], col0 + v * kBlock, acc[v][r], 1);
-    } else {
-#pragma unroll
-      for (int r = 0; r < R; ++r) store16(dp[r], col0 + v * kBlock, acc[v][r], 0);
-    }
+    combine_store<K, R, UNITS, (NT >> 1)>(a, x, dp, col0);
   }
 }
 
@@ -396,9 +126,9 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
 // (store16t: 0 plain, 1 nt).  The production
 // instantiations (gf_spec.hip) all load `nt` and select the store policy per
 // launch.
-template <int K, int R, int UNITS, int VEC = 1, int SLICES = 3, int NT = 3>
+template <int K, int R, int UNITS, int NT = 3>
 __global__ __launch_bounds__(kBlock) void gf_apply(ApplyArgs a) {
-  gf_apply_body<K, R, UNITS, VEC, SLICES, NT>(a);
+  gf_apply_body<K, R, UNITS, NT>(a);
 }
 
 // ---------------------------------------------- one-stripe inline form ----
@@ -411,17 +141,8 @@ __global__ __launch_bounds__(kBlock) void gf_apply(ApplyArgs a) {
 // kernarg segment.  One launch covers the whole shard: blocks below
 // nblk_vec do 16-B columns (the production combine, unit structure UNITS),
 // the blocks after them one byte per lane for the tail [byte0, size) -- or
-// every byte when a pointer is not 16-B aligned (nvec = 0).
-struct InlineArgs {
-  const uint8_t* src[kMaxSpecK];
-  uint8_t* dst[kMaxRows];
-  int64_t nvec, size, byte0;
-  int nblk_vec;
-  int pad_;
-  uint32_t ptab[kMaxRows * kMaxSpecK * kP3Words];  // [R][K][kP3Words], this launch's rows
-};
-static_assert(sizeof(InlineArgs) <= 4096, "kernel arguments are limited to 4 KiB");
-
+// every byte when a pointer is not 16-B aligned (nvec = 0).  The argument
+// block InlineArgs is in gf_device.hpp.
 template <int K, int R, int UNITS>
 __device__ __forceinline__ void inl_column(const uint8_t* const (&sp)[K], uint8_t* const (&dp)[R],
                                            const kconst_u32* t, int64_t col) {
@@ -497,9 +218,6 @@ __global__ __launch_bounds__(kBlock) void gf_apply_inl(InlineArgs a) {
 // only at the end does a 4x4 byte transpose (8 v_perm per dword for R = 4)
 // turn "byte position b holds all rows" into "row r holds all positions".
 // A 16-entry table of 4-B entries spans 16 distinct banks: no conflicts.
-typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-
 __device__ __forceinline__ uint32_t lds_word(lds_u8* base, uint32_t byte_off) {
   return *(lds_u32*)(base + byte_off);  // C cast: byte address -> dword load (ds_read_b32)
 }
@@ -636,24 +354,6 @@ __global__ __launch_bounds__(kBlock) void gf_apply_perm_generic(ApplyArgs a) {
 #pragma unroll
   for (int r = 0; r < R; ++r) store16t<1>(dp[r], col, acc[r]);
 }
-
-// --------------------------------------- bytes: tails, misaligned shards ----
-// One lane per byte in [byte0, size); any K, R <= kMaxRows, any alignment.
-[[maybe_unused]] static __global__ __launch_bounds__(kBlock) void gf_apply_bytes(ApplyArgs a) {
-  const int64_t x = a.byte0 + int64_t(blockIdx.x) * kBlock + threadIdx.x;
-  if (x >= a.size) return;
-  const int s = blockIdx.y;
-  const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
-  uint8_t* const* dp = a.dst + int64_t(s) * a.dst_stride + a.row0;
-  uint32_t acc[kMaxRows] = {0u, 0u, 0u, 0u};
-  for (int j = 0; j < a.K; ++j) {
-    const uint32_t v = sp[j][x];
-    const uint32_t s0 = v & 3u, s1 = (v >> 2) & 3u, s2 = (v >> 4) & 3u, s3 = v >> 6;
-    for (int r = 0; r < a.R; ++r) acc[r] ^= gf_mul_perm(a.qtab[r * a.K + j], s0, s1, s2, s3);
-  }
-  for (int r = 0; r < a.R; ++r) dp[r][x] = uint8_t(acc[r]);
-}
-
 
 }  // namespace dev
 }  // namespace ecgpu

@@ -1,8 +1,10 @@
 // gf_kernels_wide.hpp -- w = 16 / 32 kernels: the v_perm form generalised to
 // wider words, the LDS nibble-table kernels (32-bit entries, packed w = 16 pairs)
-// and the pipelined-load form.  Included through gf_kernels.hpp.
+// and the pipelined-load form, on the device vocabulary of gf_device.hpp.
+// Included by wide_spec.hip and dispatch_wide.hip, and through gf_kernels.hpp
+// (the overview) by the tools and the diagnostic library.
 #pragma once
-#include "gf_kernels_w8.hpp"
+#include "gf_device.hpp"
 
 namespace ecgpu {
 namespace dev {

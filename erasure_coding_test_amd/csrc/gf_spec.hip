@@ -2,6 +2,7 @@
 // (gf_spec.hpp).  Built four times: -DECGPU_SPEC_R=1..4.
 #include <hip/hip_runtime.h>
 
+#include "gf_kernels_w8.hpp"
 #include "gf_spec.hpp"
 
 #ifndef ECGPU_SPEC_R
@@ -16,9 +17,9 @@ constexpr int kUnitVariants[5] = {dev::kUnitNone, dev::kUnitCol0, dev::kUnitRow0
                                   dev::kUnitAll};
 
 // NT: loads always non-temporal (bit 0), NT >> 1 = store policy
-// (gf_kernels.hpp store16t: 0 plain, 1 nt)
+// (gf_device.hpp store16t: 0 plain, 1 nt)
 template <int K, int U, int STORE>
-constexpr SpecKernelFn apply_fn() { return &dev::gf_apply<K, kR, kUnitVariants[U], 1, 3, 1 | (STORE << 1)>; }
+constexpr SpecKernelFn apply_fn() { return &dev::gf_apply<K, kR, kUnitVariants[U], 1 | (STORE << 1)>; }
 
 template <int K, int S>
 struct Pol {

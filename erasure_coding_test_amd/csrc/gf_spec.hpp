@@ -1,10 +1,11 @@
 // gf_spec.hpp -- the compile-time-specialised production kernels
-// (gf_kernels.hpp gf_apply<K, R, UNITS, 1, 3, NT> and gf_apply_lds<K, R>)
+// (gf_kernels_w8.hpp gf_apply<K, R, UNITS, NT> and gf_apply_lds<K, R>)
 // for K = 1..kMaxSpecK sources.  Instantiated in four translation units, one
 // per output-row count R (gf_spec.hip built with -DECGPU_SPEC_R=1..4), so
-// the build compiles them in parallel.
+// the build compiles them in parallel.  This header needs only the argument
+// types (gf_device.hpp): the units that include it compile no kernel.
 #pragma once
-#include "gf_kernels.hpp"
+#include "gf_device.hpp"
 
 namespace ecgpu {
 
@@ -13,10 +14,10 @@ using InlineKernelFn = void (*)(dev::InlineArgs);
 constexpr int kStorePolicies = 2;
 
 // store_pol: store cache policy of the production kernel, 0 plain, 1 nt
-// (gf_kernels.hpp store16t; loads are always
+// (gf_device.hpp store16t; loads are always
 // non-temporal).  lds: the LDS nibble-table kernel instead.
-// unit_variant indexes kUnitVariants (ecgpu_runtime.hip).  nullptr if K is
-// outside 1..kMaxSpecK.
+// unit_variant indexes kUnitVariants (gf_spec.hip; runtime.hpp unit_variant
+// computes it).  nullptr if K is outside 1..kMaxSpecK.
 SpecKernelFn spec_kernel_r1(bool lds, int K, int unit_variant, int store_pol);
 SpecKernelFn spec_kernel_r2(bool lds, int K, int unit_variant, int store_pol);
 SpecKernelFn spec_kernel_r3(bool lds, int K, int unit_variant, int store_pol);

@@ -22,6 +22,7 @@
 #include "cpu_fallback.hpp"
 #include "ecgpu.h"
 #include "gf_host.hpp"
+#include "gf_kernels_packets.hpp"
 #include "matrix_host.hpp"
 #include "planner.hpp"
 #include "schedule_host.hpp"

@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "ecgpu.h"
-#include "gf_kernels.hpp"
+#include "gf_device.hpp"
 #include "gf_spec.hpp"
 #include "knobs.hpp"
 #include "planner.hpp"
@@ -141,7 +141,7 @@ inline hipError_t launch(KernelFn fn, dim3 grid, dim3 block, ecgpu::dev::ApplyAr
 }
 
 // dispatch_w8.hip: which compile-time unit structure holds exactly for rows
-// [r0, r0 + R) (gf_kernels_w8.hpp UnitMask index), the residency cap's
+// [r0, r0 + R) (gf_device.hpp UnitMask index), the residency cap's
 // dynamic LDS bytes for a launch streaming `streams` shards per lane, and
 // whether a launch takes the cap
 int unit_variant(const std::vector<uint32_t>& coef, int K, int r0, int R);

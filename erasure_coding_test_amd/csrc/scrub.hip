@@ -1,7 +1,8 @@
 // scrub.hip -- stripe scrub (ecgpu_scrub_* in include/ecgpu.h): a fused
-// parity verify with shard blame over device-resident stripes.  The kernels
-// are in scrub_kernels.hpp (specialised in scrub_spec.hip); this file is the
-// scrub object, its launch sequence and its C ABI.
+// parity verify with shard blame over device-resident stripes.  The column
+// kernel is in scrub_kernels.hpp (specialised in scrub_spec.hip); this file
+// is the init, byte and locate kernels, the scrub object, its launch sequence
+// and its C ABI.
 //
 // A scrub owns two internal plans (runtime.hpp ecgpu_plan): `mat` carries
 // the m x k coding matrix's tables and the pointer tables (rows = m, nsrc =
@@ -21,11 +22,128 @@
 #include "gf_host.hpp"
 #include "knobs.hpp"
 #include "runtime.hpp"
+#include "scrub_kernels.hpp"
 #include "scrub_spec.hpp"
 
 using namespace ecgpu;
 using namespace ecgpu::rt;
 using dev::ScrubArgs;
+
+// The non-template kernels (overview: scrub_kernels.hpp).
+namespace ecgpu {
+namespace dev {
+
+// ------------------------------------------------------------- init ----
+static __global__ __launch_bounds__(kBlock) void scrub_init(ScrubArgs a) {
+  const int s = int(blockIdx.x) * kBlock + int(threadIdx.x);
+  if (s >= a.stripes) return;
+  ecgpu_scrub_result* r = a.res + s;
+#pragma unroll
+  for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) r->bad_bytes[i] = 0;
+  r->bad_cols = 0;
+  r->first_bad = ~uint64_t(0);
+  const int n = a.k + a.m;
+  r->blame = n >= 64 ? ~uint64_t(0) : (uint64_t(1) << n) - 1;
+}
+
+// --------------------------------------------------- verify, bytes ----
+// One lane per byte in [byte0, size); runtime k and m <= ECGPU_SCRUB_MAX_M.
+static __global__ __launch_bounds__(kBlock) void scrub_verify_bytes(ScrubArgs a) {
+  const int64_t x = a.byte0 + int64_t(blockIdx.x) * kBlock + threadIdx.x;
+  if (x >= a.size) return;
+  const int s = blockIdx.y;
+  const uint8_t* const* dp = a.data + int64_t(s) * a.k;
+  const uint8_t* const* cp = a.coding + int64_t(s) * a.m;
+  uint32_t syn[ECGPU_SCRUB_MAX_M];
+#pragma unroll
+  for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) syn[i] = i < a.m ? uint32_t(cp[i][x]) : 0u;
+  for (int j = 0; j < a.k; ++j) {
+    const uint32_t v = dp[j][x];
+    const uint32_t s0 = v & 3u, s1 = (v >> 2) & 3u, s2 = (v >> 4) & 3u, s3 = v >> 6;
+#pragma unroll
+    for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i)
+      if (i < a.m) syn[i] ^= gf_mul_perm(a.qtab[i * a.k + j], s0, s1, s2, s3) & 0xFFu;
+  }
+  uint32_t any = 0;
+#pragma unroll
+  for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) any |= syn[i];
+  const uint64_t bad_lanes = wave_ballot(any != 0u);
+  if (bad_lanes == 0) return;
+  uint32_t rows[ECGPU_SCRUB_MAX_M];
+#pragma unroll
+  for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) rows[i] = uint32_t(__popcll(wave_ballot(syn[i] != 0u)));
+  const int first_lane = __ffsll((long long)bad_lanes) - 1;
+  if ((int(threadIdx.x) & 63) == first_lane)
+    scrub_publish<ECGPU_SCRUB_MAX_M>(a.res + s, rows, uint32_t(__popcll(bad_lanes)), uint64_t(x));
+}
+
+// ----------------------------------------------------------- locate ----
+// blame[s] &= candidates(x) for every bad position x of a bad stripe.  A
+// coding shard p is a candidate at x iff syn[i] == 0 for all i != p; a data
+// shard j iff syn[i] == D[i][j] * syn[pivot[j]] for all i, D[i][j] =
+// matrix[i][j] / matrix[pivot[j]][j] (host: ecgpu_scrub_blame_matrix) -- i.e.
+// the syndrome is a multiple of column j, tested without a division.  A
+// grid-stride loop with a block-uniform trip count keeps every lane in the
+// closing wave reduction; one atomicAnd per wave that narrowed the mask.
+constexpr int kLocateBlocks = 256;
+
+static __global__ __launch_bounds__(kBlock) void scrub_locate(ScrubArgs a) {
+  const int s = blockIdx.y;
+  ecgpu_scrub_result* res = a.res + s;
+  if (res->bad_cols == 0) return;  // written by the verify kernels earlier on the stream
+  const uint8_t* const* dp = a.data + int64_t(s) * a.k;
+  const uint8_t* const* cp = a.coding + int64_t(s) * a.m;
+  const int n = a.k + a.m;
+  const uint64_t all = n >= 64 ? ~uint64_t(0) : (uint64_t(1) << n) - 1;
+  uint64_t cand = all;
+  const int64_t step = int64_t(gridDim.x) * kBlock;
+  for (int64_t base = int64_t(blockIdx.x) * kBlock; base < a.size; base += step) {
+    const int64_t x = base + threadIdx.x;
+    if (x >= a.size) continue;
+    uint32_t syn[ECGPU_SCRUB_MAX_M];
+#pragma unroll
+    for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) syn[i] = i < a.m ? uint32_t(cp[i][x]) : 0u;
+    for (int j = 0; j < a.k; ++j) {
+      const uint32_t v = dp[j][x];
+      const uint32_t s0 = v & 3u, s1 = (v >> 2) & 3u, s2 = (v >> 4) & 3u, s3 = v >> 6;
+#pragma unroll
+      for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i)
+        if (i < a.m) syn[i] ^= gf_mul_perm(a.qtab[i * a.k + j], s0, s1, s2, s3) & 0xFFu;
+    }
+    uint32_t nzrows = 0;  // bit i: syn[i] != 0
+#pragma unroll
+    for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) nzrows |= (syn[i] != 0u ? 1u : 0u) << i;
+    if (nzrows == 0) continue;  // a good position constrains nothing
+    uint64_t mask = 0;
+    if ((nzrows & (nzrows - 1u)) == 0u) mask |= uint64_t(nzrows) << a.k;  // one row only: its coding shard
+    for (int j = 0; j < a.k; ++j) {
+      const int pj = a.pivot[j];
+      if (pj < 0) continue;
+      uint32_t sp = 0;
+#pragma unroll
+      for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i) sp = i == pj ? syn[i] : sp;
+      const uint32_t s0 = sp & 3u, s1 = (sp >> 2) & 3u, s2 = (sp >> 4) & 3u, s3 = sp >> 6;
+      bool ok = true;
+#pragma unroll
+      for (int i = 0; i < ECGPU_SCRUB_MAX_M; ++i)
+        if (i < a.m) ok &= syn[i] == (gf_mul_perm(a.dtab[i * a.k + j], s0, s1, s2, s3) & 0xFFu);
+      if (ok) mask |= uint64_t(1) << j;
+    }
+    cand &= mask;
+  }
+  // every lane of the block is back here (the loop's `continue`s reconverge)
+  uint32_t lo = uint32_t(cand), hi = uint32_t(cand >> 32);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    lo &= uint32_t(__shfl_xor(int(lo), o));
+    hi &= uint32_t(__shfl_xor(int(hi), o));
+  }
+  cand = (uint64_t(hi) << 32) | lo;
+  if ((threadIdx.x & 63u) == 0u && cand != all) atomicAnd(reinterpret_cast<u64a*>(&res->blame), u64a(cand));
+}
+
+}  // namespace dev
+}  // namespace ecgpu
 
 struct ecgpu_scrub {
   int device = 0, k = 0, m = 0;
@@ -114,9 +232,8 @@ int scrub_launch(ecgpu_scrub* sc, hipStream_t stream) {
     for (uint32_t c : p->coef) mul_terms += c > 1u;
     if (cap_for(K, R, mul_terms)) lds = residency_lds_bytes(sc->device, K + R);
   }
-  constexpr int kMaxGridY = 65535;
-  for (int s0 = 0; s0 < p->stripes; s0 += kMaxGridY) {
-    const int ns = std::min(kMaxGridY, p->stripes - s0);
+  for (int s0 = 0; s0 < p->stripes; s0 += dev::kMaxGridY) {
+    const int ns = std::min(dev::kMaxGridY, p->stripes - s0);
     a.data = p->d_src + size_t(s0) * K;
     a.coding = p->d_dst + size_t(s0) * R;
     a.res = sc->d_res + s0;

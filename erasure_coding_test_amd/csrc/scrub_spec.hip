@@ -2,6 +2,7 @@
 // (scrub_spec.hpp).  Built four times: -DECGPU_SPEC_R=1..4.
 #include <hip/hip_runtime.h>
 
+#include "scrub_kernels.hpp"
 #include "scrub_spec.hpp"
 
 #ifndef ECGPU_SPEC_R

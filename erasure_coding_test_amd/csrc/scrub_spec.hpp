@@ -4,9 +4,12 @@
 // translation units, one per R (scrub_spec.hip built with
 // -DECGPU_SPEC_R=1..4), like gf_spec.hpp.
 #pragma once
-#include "scrub_kernels.hpp"
+#include "gf_device.hpp"
 
 namespace ecgpu {
+namespace dev {
+struct ScrubArgs;  // scrub_kernels.hpp
+}
 
 using ScrubKernelFn = void (*)(dev::ScrubArgs);
 

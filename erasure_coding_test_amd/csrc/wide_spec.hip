@@ -2,6 +2,7 @@
 // (wide_spec.hpp).  Built four times: -DECGPU_SPEC_R=1..4.
 #include <hip/hip_runtime.h>
 
+#include "gf_kernels_wide.hpp"
 #include "wide_spec.hpp"
 
 #ifndef ECGPU_SPEC_R

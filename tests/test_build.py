@@ -70,6 +70,13 @@ def test_kernel_families_have_their_own_build_ids(tmp_path):
         assert ids["build"] != base["build"] or name.startswith("diag_kernels"), name
     for name in ("gf_kernels_w8.hpp", "gf_spec.hip", "dispatch_w8.hip"):
         assert _ids_with_edit(b, tmp_path, name)["kernels"] != base["kernels"], name
+    # a w = 8 kernel body is in no other family; the device vocabulary is in all four;
+    # the lab forms are in none, nor in the library's ID
+    w8 = _ids_with_edit(b, tmp_path, "gf_kernels_w8.hpp")
+    assert all(w8[f] == base[f] for f in ("wide", "packets", "scrub")), w8
+    voc = _ids_with_edit(b, tmp_path, "gf_device.hpp")
+    assert all(voc[f] != base[f] for f in ("kernels", "wide", "packets", "scrub")), voc
+    assert _ids_with_edit(b, tmp_path, "diag_kernels_w8.hpp") == base
     assert _ids_with_edit(b, tmp_path, "gf_kernels_wide.hpp")["wide"] != base["wide"]
     assert _ids_with_edit(b, tmp_path, "gf_kernels_packets.hpp")["packets"] != base["packets"]
     # the defaults of the knobs a family's dispatch reads are part of its ID, others are not
@@ -78,6 +85,61 @@ def test_kernel_families_have_their_own_build_ids(tmp_path):
     pipe = _ids_with_edit(b, tmp_path, "knobs.cpp", ('{"ECGPU_WIDE_PIPE", "wide_pipe", 1}',
                                                      '{"ECGPU_WIDE_PIPE", "wide_pipe", 2}'))
     assert pipe["kernels"] == base["kernels"] and pipe["wide"] != base["wide"]
+
+
+KERNEL_HEADERS = ("gf_kernels_w8.hpp", "gf_kernels_wide.hpp", "gf_kernels_packets.hpp", "scrub_kernels.hpp")
+
+
+def _closures(b):
+    """{unit source: names of the source and of its include closure}; the spec
+    units, built four times, appear once."""
+    return {src: {src} | {os.path.basename(h) for h in b.include_closure(os.path.join(b.CSRC, src))}
+            for src in sorted({u[0] for u in b.HIP_UNITS})}
+
+
+def test_objects_depend_on_the_headers_they_include():
+    b = _build_module()
+    for src in b.DROPIN_SRCS:  # the hand-kept list this replaces missed it: a stale libjerasure_amd.so
+        deps = b.include_closure(os.path.join(b.CSRC, src), dropin=True)
+        assert os.path.join(b.CSRC, "surface_cpu.hpp") in deps, src
+        assert os.path.join(b.INCLUDE, "dropin", "jerasure.h") in deps, src
+    units = _closures(b)
+    for src, deps in units.items():
+        assert not deps & {"diag_kernels_w8.hpp", "gf_kernels.hpp"}, src
+    for src in ("plans.hip", "devices.hip", "contexts.hip", "host_memory.hip", "accum.hip", "pipeline.hip"):
+        assert not units[src] & set(KERNEL_HEADERS), src
+
+
+def test_each_non_template_kernel_is_compiled_into_one_unit():
+    """A non-template __global__ in a header is emitted by every unit that
+    includes it: its file must reach exactly one unit of libecgpu.so."""
+    import re
+    b = _build_module()
+    units = _closures(b)
+    found = {}
+    for name in sorted(os.listdir(b.CSRC)):
+        if name.startswith("diag_kernels") or not name.endswith((".hip", ".hpp")):
+            continue
+        text = open(os.path.join(b.CSRC, name)).read()
+        # every __global__ definition; a template's is preceded by its template header
+        for m in re.finditer(r"(?:\[\[maybe_unused\]\]\s+)?(?:static\s+)?__global__\b[^;{]*?\bvoid\s+(\w+)\s*\(", text):
+            if not text[:m.start()].rstrip().endswith(">"):
+                found[m.group(1)] = name
+    assert sorted(found) == ["gf_apply_bytes", "gf_xor_packets_bytes", "scrub_init", "scrub_locate",
+                             "scrub_verify_bytes"], found
+    for kernel, name in found.items():
+        assert len([src for src, deps in units.items() if name in deps]) == 1, (kernel, name)
+
+
+def test_family_ids_cover_the_device_code_their_units_include():
+    b = _build_module()
+    units = _closures(b)
+    for family, (files, _) in b.KERNEL_FAMILIES.items():
+        for src in (f for f in files if f.endswith(".hip")):
+            for dep in units[src]:
+                text = open(os.path.join(b.CSRC if os.path.exists(os.path.join(b.CSRC, dep)) else b.INCLUDE, dep)).read()
+                if dep.endswith((".hpp", ".h")) and ("__global__" in text or "__device__" in text):
+                    assert dep in files, (family, src, dep)
 
 
 def test_lab_kernels_are_not_in_the_production_library():

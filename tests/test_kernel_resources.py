@@ -49,7 +49,7 @@ def usage(tmp_path_factory):
     lines = ['#include "gf_kernels.hpp"', "namespace ecgpu {", "namespace dev {"]
     for K, R, U in SHAPES:
         for nt in (1, 3):  # loads nt; stores plain / nt (gf_spec.hip apply_fn)
-            lines.append(f"template __global__ void gf_apply<{K}, {R}, {U}, 1, 3, {nt}>(ApplyArgs);")
+            lines.append(f"template __global__ void gf_apply<{K}, {R}, {U}, {nt}>(ApplyArgs);")
     lines += ["}", "}"]
     src = d / "instantiate.hip"
     src.write_text("\n".join(lines) + "\n")
@@ -59,7 +59,7 @@ def usage(tmp_path_factory):
     assert r.returncode == 0, r.stderr[-2000:]
     out, cur = {}, None
     for ln in r.stderr.splitlines():
-        m = re.search(r"Function Name: \S*gf_applyILi(\d+)ELi(\d+)ELi(\d+)ELi1ELi3ELi(\d+)E", ln)
+        m = re.search(r"Function Name: \S*gf_applyILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEEv", ln)
         if "Function Name:" in ln:
             cur = tuple(int(x) for x in m.groups()) if m else None
             if cur:
@@ -76,7 +76,7 @@ def usage(tmp_path_factory):
     asm = (d / "out.s").read_text()
     for key in out:
         K, R, U, nt = key
-        body = re.search(r"^_ZN5ecgpu3dev8gf_applyILi%dELi%dELi%dELi1ELi3ELi%dEEEvNS0_9ApplyArgsE:[^\n]*\n(.*?)s_endpgm"
+        body = re.search(r"^_ZN5ecgpu3dev8gf_applyILi%dELi%dELi%dELi%dEEEvNS0_9ApplyArgsE:[^\n]*\n(.*?)s_endpgm"
                          % key, asm, re.S | re.M).group(1)
         out[key].update(v_perm=body.count("v_perm_b32"), v_bitop3=body.count("v_bitop3_b32"),
                         vector_loads=len(re.findall(r"^\s+(?:global|flat|buffer)_load", body, re.M)),
@@ -95,7 +95,7 @@ def test_production_kernels_fit_the_residency_the_dispatcher_assumes(usage, K, R
         u = usage.get((K, R, U, nt))
         assert u and {"vgprs", "agprs", "scratch", "occupancy"} <= set(u), (K, R, U, nt, u, sorted(usage))
         by_regs = min(MAX_WAVES, VGPR_FILE // (-(-(u["vgprs"] + u["agprs"]) // VGPR_GRANULE) * VGPR_GRANULE))
-        print(f"gf_apply<{K},{R},{U},1,3,{nt}>: {u}, {by_regs} waves/SIMD by registers")
+        print(f"gf_apply<{K},{R},{U},{nt}>: {u}, {by_regs} waves/SIMD by registers")
         assert u["scratch"] == 0, (K, R, U, nt, u)
         assert by_regs >= need and u["occupancy"] >= need, (K, R, U, nt, u, need)
         # the K shard loads are the only vector loads: pointers and 3-bit-slice tables stay scalar loads

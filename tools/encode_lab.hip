@@ -26,8 +26,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "diag_kernels_w8.hpp"
 #include "gf_host.hpp"
-#include "gf_kernels.hpp"
 #include "matrix_host.hpp"
 #include "shard_stride.hpp"
 
@@ -44,7 +44,7 @@ using namespace ecgpu::dev;
   } while (0)
 
 namespace lab {
-// gf_apply<K, R, UNITS> (VEC 1, 3-bit slices, nt loads and stores) with a
+// gf_apply<K, R, UNITS> (nt loads and stores) with a
 // BS-thread workgroup.
 template <int K, int R, int UNITS, int BS>
 __global__ __launch_bounds__(BS) void enc_bs(ApplyArgs a) {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(BS) void enc_bs(ApplyArgs a) {
   u32x4 x[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) x[j] = load16t<1>(sp[j], col);
-  combine_store<K, R, UNITS, 3, 1>(a, x, dp, col);
+  combine_store<K, R, UNITS, 1>(a, x, dp, col);
 }
 
 // Early unit row: for a Vandermonde encode (row 0 and column 0 all ones) row
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void enc_sync(ApplyArgs a) {
   if constexpr (WHERE == 0) __syncthreads();
   if constexpr (WHERE == 2) __builtin_amdgcn_s_barrier();
   u32x4 acc[R];
-  combine<K, R, UNITS, 3>(a, x, acc);
+  combine<K, R, UNITS>(a, x, acc);
   if constexpr (WHERE == 1) __syncthreads();
   if (!live) return;
 #pragma unroll
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void enc_sb(ApplyArgs a) {
 #pragma unroll
   for (int j = 0; j < K; ++j) x[j] = load16t<1>(src[j], col);
   __builtin_amdgcn_sched_barrier(0);
-  combine_store<K, R, UNITS, 3, 1>(a, x, dp, col);
+  combine_store<K, R, UNITS, 1>(a, x, dp, col);
 }
 // ---- residency lab (--resid 1 / 2): which register budget and which cap
 // the R >= 3 kernels should run at.  Until this lab the production body went
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WV, WV))) v
   u32x4 x[K];
 #pragma unroll
   for (int j = 0; j < K; ++j) x[j] = load16t<1>(sp[j], col);
-  combine_store<K, R, UNITS, 3, 1>(a, x, dp, col);
+  combine_store<K, R, UNITS, 1>(a, x, dp, col);
 }
 template <int K, int R>
 __global__ __launch_bounds__(256) void xor_mix(ApplyArgs a) {
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void xor_mix(ApplyArgs a) {
 }  // namespace lab
 
 bool g_early0 = false;  // --early0 1: skew mode also times lab::enc_early0 on every slab
-bool g_vec2 = false;    // --vec2 1: ... and the production body with two columns per lane (VEC = 2)
+bool g_vec2 = false;    // --vec2 1: ... and two columns per lane (diag_kernels_w8.hpp gf_apply_vec, VEC = 2)
 bool g_dense = false;   // --dense 1: a C4-like dense 4 x 10 map (no 0 / 1 coefficients) instead of the encode
 int g_sched = 0;        // --sched 1: production vs lab::enc_sb (all loads issued before the arithmetic)
 bool g_lost = false;    // --lost 1 (with --m 1): the lost-parity decode's map -- row 2 of the RS(k,4) Vandermonde matrix
@@ -580,7 +580,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
   constexpr int U = m == 1 ? kUnitCol0 : kUnitCol0 | kUnitRow0, N = kUnitNone;
   // bs < 0: the persistent pipelined form (a resident round of |bs| workgroups per CU)
   using V = Variant;
-  const void* const vperm = reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>);
+  const void* const vperm = reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>);
   const void* const ldsk = reinterpret_cast<const void*>(&gf_apply_lds<k, m>);
   const int cap = k + m <= 9 ? 4 : 3;  // dispatch_w8.hip residency_lds_bytes
   const unsigned lds_cap = ((unsigned(163840 / cap) & ~511u) - 128u * k - 4096u) & ~4095u;
@@ -603,7 +603,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
           V{"win8_cap3", w8, 256, 3},        V{"winall_cap3", wall, 256, 3},   V{"win6_cap2", w6, 256, 2},
           V{"win8_cap2", w8, 256, 2},        V{"winall_cap2", wall, 256, 2},   V{"win4_cap4", w4, 256, 4},
           V{"win8_cap4", w8, 256, 4},        V{"winall_cap4", wall, 256, 4},   V{"seq_cap4", seq, 256, 4},
-          V{"prod_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, X, 1, 3, 3>), 256, 3},
+          V{"prod_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, X, 3>), 256, 3},
       };
     return std::vector<Variant>{
         V{"byref_uncapped", par, 256, 0},        V{"byref_cap2", par, 256, 2},
@@ -622,9 +622,9 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
                                                : resid_set(std::integral_constant<int, U>{}))
                             : g_sched == 2 ? std::vector<Variant>{  // the R = 1 levers (lost parity)
       V{"prod", vperm, 256, cap},
-      V{"vec2_cap2", reinterpret_cast<const void*>(&gf_apply<k, m, U, 2, 3, 3>), 256, 2, 0, 512},
-      V{"vec2_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, U, 2, 3, 3>), 256, 3, 0, 512},
-      V{"vec2_uncapped", reinterpret_cast<const void*>(&gf_apply<k, m, U, 2, 3, 3>), 256, 0, 0, 512},
+      V{"vec2_cap2", reinterpret_cast<const void*>(&gf_apply_vec<k, m, U, 2>), 256, 2, 0, 512},
+      V{"vec2_cap3", reinterpret_cast<const void*>(&gf_apply_vec<k, m, U, 2>), 256, 3, 0, 512},
+      V{"vec2_uncapped", reinterpret_cast<const void*>(&gf_apply_vec<k, m, U, 2>), 256, 0, 0, 512},
       V{"pipe_r3", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, U>), -3, 0},
       V{"pipe_r4", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, U>), -4, 0},
       V{"pipe_r6", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, U>), -6, 0},
@@ -632,9 +632,9 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
       V{"prod_cap2", vperm, 256, 2},
       V{"bs512_cap2", reinterpret_cast<const void*>(&lab::enc_bs<k, m, U, 512>), 512, 2},
   } : g_sched ? (g_dense ? std::vector<Variant>{
-      V{"prod_dense_uncapped", reinterpret_cast<const void*>(&gf_apply<k, m, N, 1, 3, 3>), 256, 0},
+      V{"prod_dense_uncapped", reinterpret_cast<const void*>(&gf_apply<k, m, N, 3>), 256, 0},
       V{"sb_dense_uncapped", reinterpret_cast<const void*>(&lab::enc_sb<k, m, N>), 256, 0},
-      V{"prod_dense_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, N, 1, 3, 3>), 256, 3},
+      V{"prod_dense_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, N, 3>), 256, 3},
       V{"sb_dense_cap3", reinterpret_cast<const void*>(&lab::enc_sb<k, m, N>), 256, 3},
   } : std::vector<Variant>{
       V{"prod", vperm, 256, cap},
@@ -660,7 +660,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
       V{"lds_dyn49152", ldsk, 256, 3, 49152},
       V{"lds_dyn52736", ldsk, 256, 3, 52736},
   } : g_lds ? std::vector<Variant>{
-      {"prod_bs256_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>), 256, 3},
+      {"prod_bs256_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>), 256, 3},
       {"prod_lds", reinterpret_cast<const void*>(&gf_apply_lds<k, m>), 256, 0},
       {"lds_cap3", reinterpret_cast<const void*>(&gf_apply_lds<k, m>), 256, 3},
       {"lds_cap4", reinterpret_cast<const void*>(&gf_apply_lds<k, m>), 256, 4},
@@ -668,18 +668,18 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
       {"lds_early_cap3", reinterpret_cast<const void*>(&lab::lds_early<k, m>), 256, 3},
       {"lds_early_cap4", reinterpret_cast<const void*>(&lab::lds_early<k, m>), 256, 4},
   } : g_dense ? std::vector<Variant>{
-      {"prod_dense_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, N, 1, 3, 3>), 256, 3},
-      {"dense_cap4", reinterpret_cast<const void*>(&gf_apply<k, m, N, 1, 3, 3>), 256, 4},
-      {"dense_uncapped", reinterpret_cast<const void*>(&gf_apply<k, m, N, 1, 3, 3>), 256, 0},
+      {"prod_dense_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, N, 3>), 256, 3},
+      {"dense_cap4", reinterpret_cast<const void*>(&gf_apply<k, m, N, 3>), 256, 4},
+      {"dense_uncapped", reinterpret_cast<const void*>(&gf_apply<k, m, N, 3>), 256, 0},
       {"pipe_dense_r3", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, N>), -3, 0},
       {"pipe_dense_r4", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, N>), -4, 0},
       {"pipe_dense_r5", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, N>), -5, 0},
   } : std::vector<Variant>{
-      {"prod_bs256_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>), 256, 3},
-      {"bs256_cap4", reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>), 256, 4},
+      {"prod_bs256_cap3", reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>), 256, 3},
+      {"bs256_cap4", reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>), 256, 4},
       {"pipe_r3", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, U>), -3, 0},
       {"pipe_r4", reinterpret_cast<const void*>(&lab::enc_pipe<k, m, U>), -4, 0},
-      {"bs256_cap2", reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>), 256, 2},
+      {"bs256_cap2", reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>), 256, 2},
       {"bs512_cap1", reinterpret_cast<const void*>(&lab::enc_bs<k, m, U, 512>), 512, 1},
       {"bs512_cap2", reinterpret_cast<const void*>(&lab::enc_bs<k, m, U, 512>), 512, 2},
       {"bs512_cap3", reinterpret_cast<const void*>(&lab::enc_bs<k, m, U, 512>), 512, 3},
@@ -807,8 +807,8 @@ int skew_ab(int stripes, int kib, const std::vector<int>& skews, int rounds, int
   const int blocks = k + m <= 9 ? 4 : 3;  // dispatch_w8.hip residency_lds_bytes
   const unsigned lds = unsigned(lds_cu / blocks) & ~511u;
   constexpr int U = kUnitCol0 | kUnitRow0;
-  const void* fn = reinterpret_cast<const void*>(&gf_apply<k, m, U, 1, 3, 3>);
-  const void* fn_e = g_vec2 ? reinterpret_cast<const void*>(&gf_apply<k, m, U, 2, 3, 3>)
+  const void* fn = reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>);
+  const void* fn_e = g_vec2 ? reinterpret_cast<const void*>(&gf_apply_vec<k, m, U, 2>)
                             : reinterpret_cast<const void*>(&lab::enc_early0<k, m>);
   const int per_e = g_vec2 ? 512 : 256;  // columns per workgroup of the variant
   if (g_vec2) g_early0 = true;           // the variant slot times VEC = 2 instead
