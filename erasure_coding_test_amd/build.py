@@ -18,7 +18,7 @@ library carries content IDs (ecgpu_build_id):
   0  the whole library: every source and header under csrc/ + ecgpu.h + flags
      + both compilers' --version
   1  the w = 8 kernels and their dispatch (gf_device.hpp, gf_kernels_w8.hpp,
-     gf_spec.*, dispatch_w8.hip and the defaults of the knobs it reads) + HIP flags +
+     gf_spec.*, dispatch_w8.hip with residency_w8.hpp and the defaults of the knobs it reads) + HIP flags +
      hipcc --version -- the identity a rocprofv3 PMC record of the bench's
      launches is valid for (profiles/summarize.py writes it, bench.py checks it)
   2  the same for the w = 16 / 32 kernels, 3 for the GF(2) packet kernels,
@@ -87,7 +87,7 @@ def _run_parallel(cmds):
 # (diag_kernels*) are in no family.  Every family has the device vocabulary
 # (gf_device.hpp) and its own kernel header, never another family's.
 KERNEL_FAMILIES = {
-    "kernels": (["gf_device.hpp", "gf_kernels_w8.hpp", "gf_spec.hip", "gf_spec.hpp", "dispatch_w8.hip"],
+    "kernels": (["gf_device.hpp", "gf_kernels_w8.hpp", "gf_spec.hip", "gf_spec.hpp", "dispatch_w8.hip", "residency_w8.hpp"],
                 ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_KERNEL", "ECGPU_NT"]),
     "wide": (["gf_device.hpp", "gf_kernels_wide.hpp", "wide_spec.hip", "wide_spec.hpp", "dispatch_wide.hip"],
              ["ECGPU_WIDE", "ECGPU_NIB16", "ECGPU_WIDE_UNITS", "ECGPU_WIDE_PIPE", "ECGPU_WIDE16_BPCU",

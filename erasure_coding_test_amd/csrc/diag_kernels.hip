@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "diag_kernels_w8.hpp"
+#include "residency_w8.hpp"
 
 using ecgpu::dev::ApplyArgs;
 using ecgpu::dev::u32x4;
@@ -199,6 +200,13 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
     void* dst_tab, int stripes, long long size, unsigned long long unit_mask, unsigned long long zero_mask, int nt,
     void* stream, const void* ptab) {
   KernelFn fn = nullptr;
+  // lanes per workgroup: a pick of the production gf_apply body (PROD / OCC8 below) sets the kernel's own
+  // count with the function pointer, so the two cannot disagree; every probe and lab form of this file keeps
+  // 256.  ECGPU_DIAG_LDS is bytes per workgroup whatever its size: for a one-wave kernel 16,384 B is 10 waves
+  // per CU where 54,272 B is 3 waves.
+  int lanes = 256;
+#define PROD(KK, RR, UU, NN) (lanes = ecgpu::dev::apply_block<KK, RR, UU, NN>(), &ecgpu::dev::gf_apply<KK, RR, UU, NN>)
+#define OCC8(KK, RR, UU) (lanes = ecgpu::dev::apply_block<KK, RR, UU, 3>(), &ecgpu::dev::gf_apply_occ8<KK, RR, UU>)
   if (variant == 0) {
     if (K == 10 && R == 4) fn = pick_vec<10, 4>(vec, mode);
     if (K == 10 && R == 1) fn = pick_vec<10, 1>(vec, mode);
@@ -219,29 +227,29 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
     // production gf_apply; `mode` = UnitMask
     vec = 1;
     if (K == 10 && R == 4)
-      fn = mode == 0 ? &ecgpu::dev::gf_apply<10, 4, 0> : mode == 1 ? &ecgpu::dev::gf_apply<10, 4, 1>
-                                                        : &ecgpu::dev::gf_apply<10, 4, 3>;
+      fn = mode == 0 ? PROD(10, 4, 0, 3) : mode == 1 ? PROD(10, 4, 1, 3)
+                                                        : PROD(10, 4, 3, 3);
     if (K == 10 && R == 1)
-      fn = mode == 4 ? &ecgpu::dev::gf_apply<10, 1, 4> : &ecgpu::dev::gf_apply<10, 1, 0>;
+      fn = mode == 4 ? PROD(10, 1, 4, 3) : PROD(10, 1, 0, 3);
   } else if (variant == 6) {
     vec = 1;
-    if (K == 10 && R == 4) fn = &ecgpu::dev::gf_apply_occ8<10, 4, 3>;
-    if (K == 10 && R == 1) fn = mode == 4 ? &ecgpu::dev::gf_apply_occ8<10, 1, 4> : &ecgpu::dev::gf_apply_occ8<10, 1, 0>;
+    if (K == 10 && R == 4) fn = OCC8(10, 4, 3);
+    if (K == 10 && R == 1) fn = mode == 4 ? OCC8(10, 1, 4) : OCC8(10, 1, 0);
   } else if (variant == 7) {
     // production body; vec bit0 = stripe-fastest order, bit1 = 8-wave register cap; mode = UnitMask
     const bool occ8 = (vec & 2) != 0;
     if (K == 10 && R == 4)
-      fn = occ8 ? &ecgpu::dev::gf_apply_occ8<10, 4, 3> : &ecgpu::dev::gf_apply<10, 4, 3>;
+      fn = occ8 ? OCC8(10, 4, 3) : PROD(10, 4, 3, 3);
     if (K == 10 && R == 1)
-      fn = mode == 4 ? (occ8 ? &ecgpu::dev::gf_apply_occ8<10, 1, 4> : &ecgpu::dev::gf_apply<10, 1, 4>)
-                     : (occ8 ? &ecgpu::dev::gf_apply_occ8<10, 1, 0> : &ecgpu::dev::gf_apply<10, 1, 0>);
+      fn = mode == 4 ? (occ8 ? OCC8(10, 1, 4) : PROD(10, 1, 4, 3))
+                     : (occ8 ? OCC8(10, 1, 0) : PROD(10, 1, 0, 3));
   } else if (variant == 8) {
     // production gf_apply with VEC columns per lane (vec in {1,2,4}); mode = UnitMask
     if (K == 10 && R == 4)
-      fn = vec == 1 ? &ecgpu::dev::gf_apply<10, 4, 3>
+      fn = vec == 1 ? PROD(10, 4, 3, 3)
                     : vec == 2 ? &ecgpu::dev::gf_apply_vec<10, 4, 3, 2> : &ecgpu::dev::gf_apply_vec<10, 4, 3, 4>;
     if (K == 10 && R == 1)
-      fn = vec == 1 ? &ecgpu::dev::gf_apply<10, 1, 4>
+      fn = vec == 1 ? PROD(10, 1, 4, 3)
                     : vec == 2 ? &ecgpu::dev::gf_apply_vec<10, 1, 4, 2> : &ecgpu::dev::gf_apply_vec<10, 1, 4, 4>;
   } else if (variant == 9) {
     // access-pattern probe: XOR-only gf_apply_perm over (K, R) shapes
@@ -273,8 +281,8 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
     const int ntb = vec;
     vec = 1;
 #define ECGPU_PICK(KK, RR, UU)                                                                              \
-  (variant == 13 ? (ntb == 0 ? &gf_apply<KK, RR, UU, 0> : ntb == 1 ? &gf_apply<KK, RR, UU, 1>         \
-                    : ntb == 2 ? &gf_apply<KK, RR, UU, 2> : &gf_apply<KK, RR, UU, 3>)                 \
+  (variant == 13 ? (ntb == 0 ? PROD(KK, RR, UU, 0) : ntb == 1 ? PROD(KK, RR, UU, 1)         \
+                    : ntb == 2 ? PROD(KK, RR, UU, 2) : PROD(KK, RR, UU, 3))                 \
                  : (ntb == 0 ? &gf_apply_dma<KK, RR, UU, 0> : ntb == 1 ? &gf_apply_dma<KK, RR, UU, 1> \
                     : ntb == 2 ? &gf_apply_dma<KK, RR, UU, 2> : &gf_apply_dma<KK, RR, UU, 3>))
     if (K == 10 && R == 4) fn = mode == 0 ? ECGPU_PICK(10, 4, 0) : ECGPU_PICK(10, 4, 3);
@@ -305,6 +313,8 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
     if (K == 10 && R == 4) fn = &ecgpu::dev::gf_apply_lds<10, 4>;
     if (K == 10 && R == 1) fn = &ecgpu::dev::gf_apply_lds<10, 1>;
   }
+#undef PROD
+#undef OCC8
   if (!fn) return -2;
   ApplyArgs a{};
   a.qtab = static_cast<const ecgpu::dev::u32x4*>(qtab);
@@ -323,17 +333,17 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
   a.K = K;
   a.R = R;
   a.nt = nt;
-  const long long per_block = 256LL * (variant == 0 || variant == 1 || variant == 8 ? vec : 1);
+  const long long per_block = (long long)lanes * (variant == 0 || variant == 1 || variant == 8 ? vec : 1);
   dim3 grid(unsigned((a.nvec + per_block - 1) / per_block), unsigned(stripes));
   if (variant == 3) grid = dim3(unsigned(vec), unsigned(stripes));
   if (variant == 7) {
     a.stripe_fast = vec & 1;
-    grid = a.stripe_fast ? dim3(unsigned(stripes), unsigned((a.nvec + 255) / 256))
-                         : dim3(unsigned((a.nvec + 255) / 256), unsigned(stripes));
+    grid = a.stripe_fast ? dim3(unsigned(stripes), unsigned((a.nvec + lanes - 1) / lanes))
+                         : dim3(unsigned((a.nvec + lanes - 1) / lanes), unsigned(stripes));
   }
   if (variant == 5) {  // stripe-fastest block order
     a.stripe_fast = 1;
-    grid = dim3(unsigned(stripes), unsigned((a.nvec + 255) / 256));
+    grid = dim3(unsigned(stripes), unsigned((a.nvec + lanes - 1) / lanes));
   }
   void* args[] = {&a};
   // ECGPU_DIAG_LDS: dynamic LDS bytes per block, unused by the kernels -- caps
@@ -346,6 +356,40 @@ extern "C" __attribute__((visibility("default"))) int ecgpu_diag_launch(
       hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) !=
           hipSuccess)
     return -3;
-  return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid, dim3(256), args, lds,
+  return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid, dim3(unsigned(lanes)), args, lds,
                          static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -3;
+}
+
+// What the runtime grants a production gf_apply<K, R, units> (nt loads, store
+// policy store_nt; big: the instantiation for shards above kOneWaveMaxShard)
+// under the cap allocation for waves_per_cu, which the caller states -- the
+// dispatcher's rule that picks it lives in dispatch_w8.hip, out of reach here:
+// the kernel's lanes per workgroup, the dynamic LDS bytes (residency_w8.hpp,
+// the arithmetic dispatch_w8.hip launches with) and
+// hipOccupancyMaxActiveBlocksPerMultiprocessor under them.  The bench's two
+// timed kernels and the C4 decode; -2 for any other shape.
+extern "C" __attribute__((visibility("default"))) int ecgpu_diag_apply_residency(
+    int K, int R, int units, int store_nt, int big, int waves_per_cu, int* lanes, unsigned* dyn_lds,
+    int* workgroups_per_cu) {
+  using namespace ecgpu::dev;
+  KernelFn fn = nullptr;
+  int block = 0;
+#define ECGPU_PICK1(KK, RR, UU, NN) (block = apply_block<KK, RR, UU, NN>(), &gf_apply<KK, RR, UU, NN>)
+#define ECGPU_PICK(KK, RR, UU)                                                                              \
+  (big && has_one_wave_form<KK, RR, UU>() ? (store_nt ? ECGPU_PICK1(KK, RR, UU, 7) : ECGPU_PICK1(KK, RR, UU, 5)) \
+                                           : (store_nt ? ECGPU_PICK1(KK, RR, UU, 3) : ECGPU_PICK1(KK, RR, UU, 1)))
+  if (K == 10 && R == 4 && units == 3) fn = ECGPU_PICK(10, 4, 3);
+  if (K == 10 && R == 4 && units == 0) fn = ECGPU_PICK(10, 4, 0);
+  if (K == 10 && R == 1 && units == 4) fn = ECGPU_PICK(10, 1, 4);
+#undef ECGPU_PICK
+#undef ECGPU_PICK1
+  if (!fn || !lanes || !dyn_lds || !workgroups_per_cu) return -2;
+  int device = 0, per_cu = 0;
+  if (hipGetDevice(&device) != hipSuccess ||
+      hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess)
+    return -3;
+  *lanes = block;
+  *dyn_lds = ecgpu::residency_lds_for(per_cu, ecgpu::residency_workgroups(waves_per_cu, block), 0u);
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, reinterpret_cast<const void*>(fn), block,
+                                                      *dyn_lds) == hipSuccess ? 0 : -3;
 }

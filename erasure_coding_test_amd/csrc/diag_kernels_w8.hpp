@@ -5,8 +5,10 @@
 // against the production gf_apply and not kept: the round-1
 // 2-bit PERM form with its coefficient-class modes, the production combine
 // with VEC columns per lane or with the 2-bit-slice tables, LDS-DMA loads, an
-// occupancy-8 register budget, a persistent streaming form; plus the copy
-// kernel behind the bench's copy ceiling.
+// occupancy-8 register budget, a persistent streaming form, the production
+// body at other workgroup sizes (gf_apply_wg: 64 lanes kept for two encodes up
+// to 4 MiB shards, gf_kernels_w8.hpp apply_block); plus the copy kernel behind the
+// bench's copy ceiling.
 #pragma once
 #include "gf_kernels.hpp"
 
@@ -283,10 +285,21 @@ __global__ __launch_bounds__(kBlock) void gf_apply_dma(ApplyArgs a) {
   combine_store<K, R, UNITS, (NT >> 1)>(a, x, dp, col);
 }
 
-// Same body, register budget capped for 8 waves/SIMD (<= 64 VGPRs).
+// Same body (and so the same lanes per workgroup, apply_block<K, R, UNITS, 3>()),
+// register budget capped for 8 waves/SIMD (<= 64 VGPRs).
 template <int K, int R, int UNITS>
-__global__ __launch_bounds__(kBlock, 8) void gf_apply_occ8(ApplyArgs a) {
+__global__ __launch_bounds__((apply_block<K, R, UNITS, 3>()), 8) void gf_apply_occ8(ApplyArgs a) {
   gf_apply_body<K, R, UNITS>(a);
+}
+
+// gf_apply_body itself -- both its forms: the windowed sequential one from
+// kSeqMinRows rows, every load first below -- instantiated with BS lanes per
+// workgroup; nt loads and stores.  A launch bound of 64, 128 or 256 lanes
+// leaves the compiler the same register file per wave (one wave per SIMD at
+// most), so only the column index differs between those sizes.
+template <int K, int R, int UNITS, int BS>
+__global__ __launch_bounds__(BS) void gf_apply_wg(ApplyArgs a) {
+  gf_apply_body<K, R, UNITS, 3, BS>(a);
 }
 
 // ------------------------------------------------------ PERM, streaming ----

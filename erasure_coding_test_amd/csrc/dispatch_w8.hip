@@ -23,6 +23,7 @@
 #include "gf_host.hpp"
 #include "gf_kernels_w8.hpp"
 #include "knobs.hpp"
+#include "residency_w8.hpp"
 #include "runtime.hpp"
 #include "gf_spec.hpp"
 
@@ -97,36 +98,52 @@ KernelFn generic_fn(int R) {
 // VGPRs, gf_kernels_w8.hpp) the cap governs them too, and the same rule holds
 // (profiles/r07_residency_lab.json: RS(10,4) encode 873-876 us at 2 and 3
 // per CU, 959-987 at 4-6, 1011 uncapped; RS(6,3) 752-762 at 2-5).
+// The rule is stated in waves per CU, and the workgroups per CU follow from
+// the kernel's lanes per workgroup (gf_kernels_w8.hpp apply_block, carried by
+// SpecKernel): 256-lane kernels run at 4 * kCapMaxBlocks = 16 waves per CU
+// for K + R <= 9 and 12 above, as 4 and 3 workgroups; one-wave workgroups
+// (the RS(10,4) and RS(6,3) encodes up to 4 MiB shards; above that their
+// 256-lane instantiation runs, at the 256-lane rule) at kCapWavesOneWave = 10, which the
+// 256-lane form cannot express (profiles/r09_wg_lab.json, 64 lanes at 8 / 10
+// / 12 / 14 / 16 waves per CU: RS(10,4) encode 842 / 848 / 862 / 883 / 898 us,
+// 256 lanes at 12: 866; the dense 4 x 10 map 919 / 907 / 882 / 893 / 908
+// against 895-905; RS(6,3) 731 / 722 / 733 / 745 / 759 against 756 -- 10 is
+// the one point that loses on none of them).
 // A 256-thread workgroup puts one wave on each SIMD, so a cap of N per CU is
 // real only while the kernel fits N waves on a SIMD: every specialised
 // kernel must reach kMinWavesPerSimd (tests/test_kernel_resources.py
 // compiles the bench's instantiations and checks).  The cap is an unused
-// dynamic LDS allocation of LDS_per_CU / blocks (rounded down to 512 B); at
-// most kCapMaxBlocks per CU, so never above the 64 KiB a launch may ask for
-// without raising the function's limit.  A kernel with static LDS of
+// dynamic LDS allocation of LDS_per_CU / workgroups (rounded down to 512 B);
+// at least 3 workgroups per CU, so never above the 64 KiB a launch may ask
+// for without raising the function's limit, and what the runtime grants is
+// exactly the intended count (tests/test_apply_block_gpu.py asks it).  A kernel with static LDS of
 // its own (the LDS engine's tables) gets that much less and a further 4 KiB
 // margin, rounded down to 4 KiB: RS(10,4) at "3 per CU" with 1,280 B of
 // tables, dynamic 52,736 B (1.8 KiB spare) ran at 2 per CU's speed (989 us),
 // 40,960-49,152 B at 902-905 (tools/encode_lab.hip --lds 2).
-// ECGPU_BLOCKS_PER_CU fixes the block count (0 = never cap).
+// ECGPU_BLOCKS_PER_CU fixes the residency in units of one 256-lane
+// workgroup, i.e. 4 waves, per CU (0 = never cap).
 constexpr int kCapMaxBlocks = 4;     // K + R <= 9; one fewer above
 constexpr int kMinWavesPerSimd = 4;  // what every specialised v_perm kernel's VGPR count must allow
 static_assert(kMinWavesPerSimd >= kCapMaxBlocks, "a cap above the register limit is a no-op");
-unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes) {
+constexpr int kWavesPerBlock = dev::kBlock / kLanesPerWave;  // one per SIMD
+constexpr int kCapWavesOneWave = 10;                           // one-wave workgroups, any K + R
+static_assert(kCapWavesOneWave <= kMinWavesPerSimd * kWavesPerBlock, "a cap above the register limit is a no-op");
+int residency_waves_per_cu(int streams, int lanes) {
+  const int fixed = knob(Knob::kBlocksPerCu);
+  if (fixed >= 0) return fixed * kWavesPerBlock;
+  if (lanes < dev::kBlock) return kCapWavesOneWave;
+  return (streams <= 9 ? kCapMaxBlocks : kCapMaxBlocks - 1) * kWavesPerBlock;
+}
+
+unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes, int lanes) {
   static std::once_flag once;
   static int per_cu = 0;
   std::call_once(once, [&] {
     if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) != hipSuccess)
       per_cu = 0;
   });
-  const int fixed = knob(Knob::kBlocksPerCu);
-  const int blocks = fixed >= 0 ? fixed : (streams <= 9 ? kCapMaxBlocks : kCapMaxBlocks - 1);
-  if (blocks <= 0 || per_cu <= 0) return 0;
-  const unsigned total = unsigned(per_cu / blocks) & ~511u;
-  const unsigned reserve = static_bytes ? static_bytes + 4096u : 0u;
-  if (total <= reserve) return 0;
-  const unsigned b = (total - reserve) & (static_bytes ? ~4095u : ~511u);
-  return b + static_bytes > unsigned(per_cu / (blocks + 1)) ? b : 0u;
+  return residency_lds_for(per_cu, residency_workgroups(residency_waves_per_cu(streams, lanes), lanes), static_bytes);
 }
 
 // Per-launch policy of the production kernel (A/B on MI355X in the bench's
@@ -210,7 +227,6 @@ int plan_launch(ecgpu_plan* p, hipStream_t stream) {
   const int K = p->nsrc;
   const int64_t nvec = p->aligned ? p->size / 16 : 0;
   const int64_t byte0 = nvec * 16;
-  const dim3 block(dev::kBlock);
   for (int r0 = 0; r0 < p->rows; r0 += dev::kMaxRows) {
     const int R = std::min(dev::kMaxRows, p->rows - r0);
     const bool spec = K <= dev::kMaxSpecK;
@@ -222,9 +238,12 @@ int plan_launch(ecgpu_plan* p, hipStream_t stream) {
     // an in-process interleaved A/B has v_perm 2.5 % faster on C4 decode
     // {0,1,2,3} and even on RS(12,4) {0,1,2,3}, profiles/r02_engine_ab_inprocess.json.)
     const bool use_lds = p->kind == ECGPU_KERNEL_LDS;
-    KernelFn vec_fn = spec ? spec_kernel(use_lds, K, R, unit_variant(p->coef, K, r0, R), p->nt) : generic_fn(R);
+    // the kernel and the lanes per workgroup it was compiled for travel together
+    const bool big = p->size > dev::kOneWaveMaxShard;
+    const SpecKernel vec_k = spec ? spec_kernel(use_lds, K, R, unit_variant(p->coef, K, r0, R), p->nt, big)
+                                  : SpecKernel{generic_fn(R), dev::kBlock};
+    if (!vec_k.fn || vec_k.block <= 0) return ECGPU_ERR_ARG;
     if (spec && nvec > 0) g_engine_launches[use_lds ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
-    const int vec = 1;
     // Both engines follow the cap rule; the LDS engine's allocation leaves room
     // for its K * 128 B of tables (tools/encode_lab.hip --lds: RS(10,4) encode
     // 1008 us uncapped, 902 at 3 per CU, v_perm 890).
@@ -258,14 +277,14 @@ int plan_launch(ecgpu_plan* p, hipStream_t stream) {
       a.unit_mask = unit;
       a.zero_mask = zero;
       if (nvec > 0) {
-        const int64_t per_block = int64_t(dev::kBlock) * vec;
+        const int64_t per_block = vec_k.block;
         const dim3 grid(unsigned((nvec + per_block - 1) / per_block), unsigned(ns));
-        const unsigned lds = cap ? residency_lds_bytes(p->device, K + R, static_lds) : 0u;
-        ECGPU_HIP(launch(vec_fn, grid, block, a, stream, lds));
+        const unsigned lds = cap ? residency_lds_bytes(p->device, K + R, static_lds, vec_k.block) : 0u;
+        ECGPU_HIP(launch(vec_k.fn, grid, dim3(unsigned(vec_k.block)), a, stream, lds));
       }
       if (byte0 < p->size) {
         const dim3 grid(unsigned((p->size - byte0 + dev::kBlock - 1) / dev::kBlock), unsigned(ns));
-        ECGPU_HIP(launch(&dev::gf_apply_bytes, grid, block, a, stream));
+        ECGPU_HIP(launch(&dev::gf_apply_bytes, grid, dim3(dev::kBlock), a, stream));
       }
     }
   }

@@ -48,15 +48,42 @@ constexpr int kSeqMinRows = 3;
 template <int K>
 constexpr int load_window() { return K <= 10 ? 6 : K; }
 
-// Lane l of block b handles the 16-byte column b*256 + l of every shard of
-// stripe s; R < kSeqMinRows: all K loads are issued before any arithmetic,
-// then R stores.  NT: bit 0 = non-temporal loads, NT >> 1 = store policy of
-// store16t.
-template <int K, int R, int UNITS, int NT = 3>
+// Lanes per workgroup of gf_apply<K, R, UNITS, NT>.  A workgroup is the unit
+// in which the kernel bursts -- its waves start in the same cycle and its
+// residency slot is held until the slowest of them has stored -- so one-wave
+// workgroups under a cap in waves per CU space a CU's requests out.
+// Interleaved in one process at equal waves per CU (tools/encode_lab.hip
+// --wg 1, profiles/r09_wg_lab.json): 64 lanes at 10 waves per CU beat 256
+// lanes at 12 by 2.0 % on RS(10,4) encode at 4 MiB shards (848 vs 866 us) and
+// by 4.5 % on RS(6,3) at 1 MiB, and are level on RS(10,4) at 1 MiB; at 16 MiB
+// shards they lose 31 % (1135 vs 869 us), as they do on RS(12,4) at 16 MiB,
+// and RS(12,4) is best at 256 lanes at 1 and 4 MiB too.  The dense 4 x 10 map
+// gains nothing (907 vs 895-905), nor does the R <= 2 body on decode{0} (683
+// vs 679).  So only the two encodes that were measured to gain take the
+// one-wave form, and only up to kOneWaveMaxShard bytes per shard: the shard
+// size is known at the launch, so each of them is also instantiated at 256
+// lanes under kNt256Lanes, a bit of NT that changes nothing else, and the
+// dispatcher picks by size (dispatch_w8.hip).  Every other (K, R, UNITS) has
+// one form, 256 lanes, whatever the bit says.
+constexpr int kNt256Lanes = 4;  // NT bit 2: the 256-lane instantiation of a kernel that has a one-wave form
+constexpr int64_t kOneWaveMaxShard = int64_t(4) << 20;
+template <int K, int R, int UNITS>
+constexpr bool has_one_wave_form() {
+  return UNITS == (kUnitCol0 | kUnitRow0) && ((K == 10 && R == 4) || (K == 6 && R == 3));
+}
+template <int K, int R, int UNITS, int NT>
+constexpr int apply_block() { return has_one_wave_form<K, R, UNITS>() && !(NT & kNt256Lanes) ? 64 : kBlock; }
+
+// Lane l of block b handles the 16-byte column b*BS + l of every shard of
+// stripe s (BS: apply_block of the kernel; the lab instantiates the body at
+// other sizes, diag_kernels_w8.hpp gf_apply_wg); R < kSeqMinRows: all K loads
+// are issued before any arithmetic, then R stores.  NT: bit 0 = non-temporal
+// loads, bit 1 = store policy of store16t, bit 2 = kNt256Lanes.
+template <int K, int R, int UNITS, int NT = 3, int BS = apply_block<K, R, UNITS, NT>()>
 __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
   const unsigned cblk = a.stripe_fast ? blockIdx.y : blockIdx.x;
   const int s = a.stripe_fast ? blockIdx.x : blockIdx.y;
-  const int64_t col0 = int64_t(cblk) * kBlock + threadIdx.x;
+  const int64_t col0 = int64_t(cblk) * BS + threadIdx.x;
   if (col0 >= a.nvec) return;
   const uint8_t* const* sp = a.src + int64_t(s) * a.src_stride;
   // Fetch ALL pointers before the first store: a pointer read after a store
@@ -111,23 +138,23 @@ __device__ __forceinline__ void gf_apply_body(const ApplyArgs& a) {
       u32x4 o;
 #pragma unroll
       for (int c = 0; c < 4; ++c) o[c] = xa[r][c].value();
-      store16t<(NT >> 1)>(dp[r], col0, o);
+      store16t<((NT >> 1) & 1)>(dp[r], col0, o);
     }
   } else {
     // One or two output rows (46-58 VGPRs for the R = 1 decodes).
     u32x4 x[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) x[j] = load16t<NT & 1>(sp[j], col0);
-    combine_store<K, R, UNITS, (NT >> 1)>(a, x, dp, col0);
+    combine_store<K, R, UNITS, ((NT >> 1) & 1)>(a, x, dp, col0);
   }
 }
 
-// Cache policy: NT bit 0 = non-temporal loads, NT >> 1 = store policy
+// Cache policy: NT bit 0 = non-temporal loads, bit 1 = store policy
 // (store16t: 0 plain, 1 nt).  The production
 // instantiations (gf_spec.hip) all load `nt` and select the store policy per
 // launch.
 template <int K, int R, int UNITS, int NT = 3>
-__global__ __launch_bounds__(kBlock) void gf_apply(ApplyArgs a) {
+__global__ __launch_bounds__((apply_block<K, R, UNITS, NT>())) void gf_apply(ApplyArgs a) {
   gf_apply_body<K, R, UNITS, NT>(a);
 }
 

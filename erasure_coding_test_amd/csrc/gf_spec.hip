@@ -18,13 +18,19 @@ constexpr int kUnitVariants[5] = {dev::kUnitNone, dev::kUnitCol0, dev::kUnitRow0
 
 // NT: loads always non-temporal (bit 0), NT >> 1 = store policy
 // (gf_device.hpp store16t: 0 plain, 1 nt)
-template <int K, int U, int STORE>
-constexpr SpecKernelFn apply_fn() { return &dev::gf_apply<K, kR, kUnitVariants[U], 1 | (STORE << 1)>; }
+// and, where the kernel has a one-wave form, bit 2 (dev::kNt256Lanes) its
+// 256-lane instantiation for shards above dev::kOneWaveMaxShard (BIG); every
+// other cell is one kernel under both BIG values
+template <int K, int U, int STORE, bool BIG>
+constexpr SpecKernel apply_fn() {
+  constexpr int NT = 1 | (STORE << 1) | (BIG && dev::has_one_wave_form<K, kR, kUnitVariants[U]>() ? dev::kNt256Lanes : 0);
+  return SpecKernel{&dev::gf_apply<K, kR, kUnitVariants[U], NT>, dev::apply_block<K, kR, kUnitVariants[U], NT>()};
+}
 
-template <int K, int S>
+template <int K, int S, bool BIG>
 struct Pol {
-  static constexpr SpecKernelFn apply[5] = {apply_fn<K, 0, S>(), apply_fn<K, 1, S>(), apply_fn<K, 2, S>(),
-                                            apply_fn<K, 3, S>(), apply_fn<K, 4, S>()};
+  static constexpr SpecKernel apply[5] = {apply_fn<K, 0, S, BIG>(), apply_fn<K, 1, S, BIG>(), apply_fn<K, 2, S, BIG>(),
+                                          apply_fn<K, 3, S, BIG>(), apply_fn<K, 4, S, BIG>()};
 };
 
 template <int K, int U, bool ZC>
@@ -35,14 +41,15 @@ struct Row {
   static constexpr InlineKernelFn inl[2][5] = {
       {inl_fn<K, 0, false>(), inl_fn<K, 1, false>(), inl_fn<K, 2, false>(), inl_fn<K, 3, false>(), inl_fn<K, 4, false>()},
       {inl_fn<K, 0, true>(), inl_fn<K, 1, true>(), inl_fn<K, 2, true>(), inl_fn<K, 3, true>(), inl_fn<K, 4, true>()}};
-  static constexpr const SpecKernelFn* apply[kStorePolicies] = {Pol<K, 0>::apply, Pol<K, 1>::apply};
+  static constexpr const SpecKernel* apply[2][kStorePolicies] = {{Pol<K, 0, false>::apply, Pol<K, 1, false>::apply},
+                                                                 {Pol<K, 0, true>::apply, Pol<K, 1, true>::apply}};
   static constexpr SpecKernelFn lds = &dev::gf_apply_lds<K, kR>;
 };
 
 template <int... Ks>
-SpecKernelFn pick(bool lds, int K, int u, int store_pol) {
-  SpecKernelFn out = nullptr;
-  ((K == Ks ? (out = lds ? Row<Ks>::lds : Row<Ks>::apply[store_pol][u], 0) : 0), ...);
+SpecKernel pick(bool lds, int K, int u, int store_pol, bool big) {
+  SpecKernel out;
+  ((K == Ks ? (out = lds ? SpecKernel{Row<Ks>::lds, dev::kBlock} : Row<Ks>::apply[big ? 1 : 0][store_pol][u], 0) : 0), ...);
   return out;
 }
 
@@ -57,9 +64,9 @@ InlineKernelFn pick_inl(int K, int u, bool zc) {
 
 #define ECGPU_CAT2(a, b) a##b
 #define ECGPU_CAT(a, b) ECGPU_CAT2(a, b)
-SpecKernelFn ECGPU_CAT(spec_kernel_r, ECGPU_SPEC_R)(bool lds, int K, int unit_variant, int store_pol) {
-  if (unit_variant < 0 || unit_variant > 4 || store_pol < 0 || store_pol >= kStorePolicies) return nullptr;
-  return pick<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(lds, K, unit_variant, store_pol);
+SpecKernel ECGPU_CAT(spec_kernel_r, ECGPU_SPEC_R)(bool lds, int K, int unit_variant, int store_pol, bool big) {
+  if (unit_variant < 0 || unit_variant > 4 || store_pol < 0 || store_pol >= kStorePolicies) return {};
+  return pick<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16>(lds, K, unit_variant, store_pol, big);
 }
 
 InlineKernelFn ECGPU_CAT(inline_kernel_r, ECGPU_SPEC_R)(int K, int unit_variant, bool zc) {

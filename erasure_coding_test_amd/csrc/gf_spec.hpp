@@ -10,6 +10,13 @@
 namespace ecgpu {
 
 using SpecKernelFn = void (*)(dev::ApplyArgs);
+// A specialised kernel with the lanes per workgroup it was compiled for
+// (gf_kernels_w8.hpp apply_block; kBlock for the LDS engine): the
+// launch takes its block and grid from here, never from a constant of its own.
+struct SpecKernel {
+  SpecKernelFn fn = nullptr;
+  int block = 0;
+};
 using InlineKernelFn = void (*)(dev::InlineArgs);
 constexpr int kStorePolicies = 2;
 
@@ -17,11 +24,13 @@ constexpr int kStorePolicies = 2;
 // (gf_device.hpp store16t; loads are always
 // non-temporal).  lds: the LDS nibble-table kernel instead.
 // unit_variant indexes kUnitVariants (gf_spec.hip; runtime.hpp unit_variant
-// computes it).  nullptr if K is outside 1..kMaxSpecK.
-SpecKernelFn spec_kernel_r1(bool lds, int K, int unit_variant, int store_pol);
-SpecKernelFn spec_kernel_r2(bool lds, int K, int unit_variant, int store_pol);
-SpecKernelFn spec_kernel_r3(bool lds, int K, int unit_variant, int store_pol);
-SpecKernelFn spec_kernel_r4(bool lds, int K, int unit_variant, int store_pol);
+// computes it).  big: shards above dev::kOneWaveMaxShard bytes -- the 256-lane
+// instantiation of the kernels that also have a one-wave form.  fn == nullptr
+// if K is outside 1..kMaxSpecK.
+SpecKernel spec_kernel_r1(bool lds, int K, int unit_variant, int store_pol, bool big);
+SpecKernel spec_kernel_r2(bool lds, int K, int unit_variant, int store_pol, bool big);
+SpecKernel spec_kernel_r3(bool lds, int K, int unit_variant, int store_pol, bool big);
+SpecKernel spec_kernel_r4(bool lds, int K, int unit_variant, int store_pol, bool big);
 
 // gf_apply_inl<K, R, UNITS, ZC> (one stripe, everything in the kernel
 // arguments; zc: the grid-stride form for host memory used in place);
@@ -41,13 +50,13 @@ inline InlineKernelFn inline_kernel(int K, int R, int unit_variant, bool zc) {
   }
 }
 
-inline SpecKernelFn spec_kernel(bool lds, int K, int R, int unit_variant, int store_pol) {
+inline SpecKernel spec_kernel(bool lds, int K, int R, int unit_variant, int store_pol, bool big) {
   switch (R) {
-    case 1: return spec_kernel_r1(lds, K, unit_variant, store_pol);
-    case 2: return spec_kernel_r2(lds, K, unit_variant, store_pol);
-    case 3: return spec_kernel_r3(lds, K, unit_variant, store_pol);
-    case 4: return spec_kernel_r4(lds, K, unit_variant, store_pol);
-    default: return nullptr;
+    case 1: return spec_kernel_r1(lds, K, unit_variant, store_pol, big);
+    case 2: return spec_kernel_r2(lds, K, unit_variant, store_pol, big);
+    case 3: return spec_kernel_r3(lds, K, unit_variant, store_pol, big);
+    case 4: return spec_kernel_r4(lds, K, unit_variant, store_pol, big);
+    default: return {};
   }
 }
 

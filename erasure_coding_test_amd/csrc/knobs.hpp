@@ -14,7 +14,8 @@ namespace ecgpu {
 
 enum class Knob : int {
   kCap,             // ECGPU_CAP: residency cap rule -1 auto (cap_for), 0 never, 1 always
-  kBlocksPerCu,     // ECGPU_BLOCKS_PER_CU: capped launches' workgroups per CU, -1 auto (4 / 3 by shard streams), 0 none
+  kBlocksPerCu,     // ECGPU_BLOCKS_PER_CU: capped launches' residency in 256-lane workgroups (4 waves) per CU, -1 auto
+                    // (16 / 12 waves by shard streams, 10 for one-wave workgroups), 0 none
   kKernel,          // ECGPU_KERNEL: w = 8 engine of new plans, 0 v_perm (production), 1 LDS nibble tables
   kNt,              // ECGPU_NT: store policy of new plans, 0 plain, 1 non-temporal
   kWidePerm,        // ECGPU_WIDE: 1 forces the w = 16 / 32 v_perm engine

@@ -145,7 +145,8 @@ inline hipError_t launch(KernelFn fn, dim3 grid, dim3 block, ecgpu::dev::ApplyAr
 // dynamic LDS bytes for a launch streaming `streams` shards per lane, and
 // whether a launch takes the cap
 int unit_variant(const std::vector<uint32_t>& coef, int K, int r0, int R);
-unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes = 0);
+unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes = 0, int lanes = ecgpu::dev::kBlock);
+int residency_waves_per_cu(int streams, int lanes);  // the rule behind it, in waves per CU
 bool cap_for(int K, int R, int mul_terms, bool seq = false);  // seq: the sequential R >= 3 body of gf_apply
 
 // ---- plans (plans.hip) --------------------------------------------------------

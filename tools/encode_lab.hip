@@ -15,6 +15,10 @@
 //   tools/encode_lab.bin --resid 1|2 [--dense 1] [--k 12 --m 4 --mib 16 --stripes 24]
 //       1: register budgets x residency caps of the R >= 3 body, with the XOR stream probe at every cap;
 //       2: the sequential body's load window (4 / 6 / 8 / all loads first) at 2 / 3 / 4 per CU
+//   tools/encode_lab.bin --wg 1 [--xor 1 | --lost 1 | --dense 1] [--k .. --m .. --mib .. --stripes ..]
+//       the production body (diag_kernels_w8.hpp gf_apply_wg) at 64 / 128 / 256 / 512 lanes per workgroup,
+//       every size at 8 / 12 / 16 waves per CU (64 lanes also 10 / 14; 512 lanes cannot make 12), beside
+//       the production launch; --xor 1 with --m 1 is decode{0}'s all-ones map
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -409,6 +413,8 @@ bool g_dense = false;   // --dense 1: a C4-like dense 4 x 10 map (no 0 / 1 coeff
 int g_sched = 0;        // --sched 1: production vs lab::enc_sb (all loads issued before the arithmetic)
 bool g_lost = false;    // --lost 1 (with --m 1): the lost-parity decode's map -- row 2 of the RS(k,4) Vandermonde matrix
 int g_resid = 0;        // --resid 1: register budgets x residency caps of the R >= 3 body, and the XOR stream probe at each cap
+int g_wg = 0;           // --wg 1: the production body at 64 / 128 / 256 / 512 lanes per workgroup, at equal waves per CU
+bool g_xor = false;     // --xor 1 (with --m 1): the all-ones map of decode{0}, unit structure kUnitAll
 int g_lds = 0;          // --lds 1: the LDS nibble-table engine (production form and lab forms) beside the v_perm production;
                         // --lds 2: both engines at 3 workgroups per CU under dynamic LDS allocations of several sizes
 
@@ -475,6 +481,8 @@ int main(int argc, char** argv) {
     else if (f == "--vec2") g_vec2 = std::atoi(argv[i + 1]) != 0;
     else if (f == "--dense") g_dense = std::atoi(argv[i + 1]) != 0;
     else if (f == "--resid") g_resid = std::atoi(argv[i + 1]);
+    else if (f == "--wg") g_wg = std::atoi(argv[i + 1]);
+    else if (f == "--xor") g_xor = std::atoi(argv[i + 1]) != 0;
     else if (f == "--lds") g_lds = std::atoi(argv[i + 1]);
     else if (f == "--sync") g_sync = std::atoi(argv[i + 1]);
     else if (f == "--sched") g_sched = std::atoi(argv[i + 1]);
@@ -520,6 +528,8 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
     for (int j = 0; j < k * m; ++j) M[j] = M4[2 * k + j % k];
     std::free(M4);
   }
+  if (g_xor)
+    for (int j = 0; j < k * m; ++j) M[j] = 1;  // decode{0}: the lost data shard is the XOR of the survivors and parity 0
   if (g_dense) {
     std::mt19937 gm(4);
     for (int i = 0; i < k * m; ++i) M[i] = 2 + int(gm() % 254);  // no 0 / 1: every term multiplies (C4's decode rows)
@@ -618,7 +628,33 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
         V{"xor_cap3", xr, 256, 3, 0, 0, true},     V{"xor_cap4", xr, 256, 4, 0, 0, true},
     };
   };
-  std::vector<Variant> vs = g_resid ? (g_dense ? resid_set(std::integral_constant<int, N>{})
+  // --wg: vs[0] is the production launch at the library's cap; every lab form runs at W waves per CU, i.e.
+  // W / (BS / 64) workgroups per CU through the same dynamic-LDS allocation
+  auto wg_set = [&](auto unit_tag) {
+    constexpr int X = decltype(unit_tag)::value;
+    // the production launch as dispatch_w8.hip makes it: the kernel's own lanes (its 256-lane instantiation
+    // above kOneWaveMaxShard bytes per shard) at the library's waves per CU
+    const bool big = int64_t(S) > kOneWaveMaxShard;
+    const int PB = big ? apply_block<k, m, X, 3 | kNt256Lanes>() : apply_block<k, m, X, 3>();
+    const void* const prod_fn = big ? reinterpret_cast<const void*>(&gf_apply<k, m, X, 3 | kNt256Lanes>)
+                                    : reinterpret_cast<const void*>(&gf_apply<k, m, X, 3>);
+    const int prod_waves = PB < 256 ? 10 : 4 * cap;
+    std::vector<Variant> out{V{"prod", prod_fn, PB, prod_waves / (PB / 64)}};
+    auto add = [&](const void* fn, int bs, std::initializer_list<int> waves) {
+      for (int w : waves)
+        if (w % (bs / 64) == 0)
+          out.push_back(V{"wg" + std::to_string(bs) + "_w" + std::to_string(w), fn, bs, w / (bs / 64)});
+    };
+    add(reinterpret_cast<const void*>(&gf_apply_wg<k, m, X, 64>), 64, {8, 10, 12, 14, 16});
+    add(reinterpret_cast<const void*>(&gf_apply_wg<k, m, X, 128>), 128, {8, 12, 16});
+    add(reinterpret_cast<const void*>(&gf_apply_wg<k, m, X, 256>), 256, {8, 12, 16});
+    add(reinterpret_cast<const void*>(&gf_apply_wg<k, m, X, 512>), 512, {8, 12, 16});
+    return out;
+  };
+  std::vector<Variant> vs = g_wg ? (g_dense ? wg_set(std::integral_constant<int, N>{})
+                                    : g_xor ? wg_set(std::integral_constant<int, int(kUnitAll)>{})
+                                            : wg_set(std::integral_constant<int, U>{}))
+                            : g_resid ? (g_dense ? resid_set(std::integral_constant<int, N>{})
                                                : resid_set(std::integral_constant<int, U>{}))
                             : g_sched == 2 ? std::vector<Variant>{  // the R = 1 levers (lost parity)
       V{"prod", vperm, 256, cap},
@@ -686,6 +722,16 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
       {"bs1024_cap1", reinterpret_cast<const void*>(&lab::enc_bs<k, m, U, 1024>), 1024, 1},
       {"bs1024_cap2", reinterpret_cast<const void*>(&lab::enc_bs<k, m, U, 1024>), 1024, 2},
   };
+  // The modes above name the production kernel's launch in 256-lane workgroups ("bs256", "capN" = N of them per
+  // CU).  Where the kernel is compiled for fewer lanes (gf_kernels_w8.hpp apply_block) it must be launched with
+  // those, at the same waves per CU.
+  for (Variant& v : vs) {
+    constexpr int PB = apply_block<k, m, U, 3>();  // (the dense map's kernel has 256 lanes)
+    if (v.fn == vperm && !g_wg && v.bs == 256 && PB != 256) {
+      v.bs = PB;
+      v.blocks_per_cu *= 256 / PB;
+    }
+  }
   int cus = 0;
   CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
   int dev = 0, lds_cu = 0;
@@ -758,6 +804,7 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
       }
   }
   std::vector<std::vector<float>> t(vs.size());
+  std::vector<std::string> per_round(vs.size());  // each round's median, in round order
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
@@ -773,6 +820,11 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
         CK(hipEventElapsedTime(&ms, e0, e1));
         t[v].push_back(ms * 1000.f);
       }
+      std::vector<float> rr(t[v].end() - reps, t[v].end());
+      std::sort(rr.begin(), rr.end());
+      char buf[32];
+      std::snprintf(buf, sizeof buf, "%s%.1f", rd ? ", " : "", double(rr[rr.size() / 2]));
+      per_round[v] += buf;
     }
   const double bytes = double(k + m) * double(S) * stripes;
   for (size_t v = 0; v < vs.size(); ++v) {
@@ -780,10 +832,13 @@ int variant_ab(int stripes, size_t S, int skew_kib, int rounds, int reps) {
     const double med = t[v][t[v].size() / 2];
     hipFuncAttributes fa{};
     CK(hipFuncGetAttributes(&fa, vs[v].fn));
+    int occ = 0;  // workgroups per CU the runtime grants under this allocation: what the cap came to
+    CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, vs[v].fn, vs[v].bs < 0 ? 256 : vs[v].bs, lds_of(vs[v])));
     std::printf("{\"k\": %d, \"m\": %d, \"dense\": %d, \"variant\": \"%s\", \"block\": %d, \"blocks_per_cu\": %d, \"dyn_lds\": %u, "
-                "\"vgprs\": %d, \"stripes\": %d, \"median_us\": %.1f, \"min_us\": %.1f, \"GBps\": %.0f, \"frac\": %.4f}\n",
-                k, m, int(g_dense), vs[v].name.c_str(), vs[v].bs, vs[v].blocks_per_cu, lds_of(vs[v]), fa.numRegs, stripes, med,
-                double(t[v][0]), bytes / med / 1e3, bytes / med / 1e3 / 8000.0);
+                "\"occupancy_blocks_per_cu\": %d, \"vgprs\": %d, \"stripes\": %d, \"shard_bytes\": %zu, \"median_us\": %.1f, \"min_us\": %.1f, \"GBps\": %.0f, "
+                "\"frac\": %.4f, \"round_medians_us\": [%s]}\n",
+                k, m, int(g_dense), vs[v].name.c_str(), vs[v].bs, vs[v].blocks_per_cu, lds_of(vs[v]), occ, fa.numRegs, stripes, S, med,
+                double(t[v][0]), bytes / med / 1e3, bytes / med / 1e3 / 8000.0, per_round[v].c_str());
   }
   return 0;
 }
@@ -804,10 +859,14 @@ int skew_ab(int stripes, int kib, const std::vector<int>& skews, int rounds, int
   int dev = 0, lds_cu = 0;
   CK(hipGetDevice(&dev));
   CK(hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev));
-  const int blocks = k + m <= 9 ? 4 : 3;  // dispatch_w8.hip residency_lds_bytes
-  const unsigned lds = unsigned(lds_cu / blocks) & ~511u;
   constexpr int U = kUnitCol0 | kUnitRow0;
-  const void* fn = reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>);
+  const bool big = int64_t(S) > kOneWaveMaxShard;  // dispatch_w8.hip: the 256-lane instantiation above it
+  const int PB = big ? apply_block<k, m, U, 3 | kNt256Lanes>() : apply_block<k, m, U, 3>();
+  const int waves = PB < 256 ? 10 : (k + m <= 9 ? 16 : 12);  // dispatch_w8.hip residency_waves_per_cu
+  const unsigned lds = unsigned(lds_cu / (waves / (PB / 64))) & ~511u;
+  const unsigned lds_e = unsigned(lds_cu / (k + m <= 9 ? 4 : 3)) & ~511u;  // the 256-lane variant slot
+  const void* fn = big ? reinterpret_cast<const void*>(&gf_apply<k, m, U, 3 | kNt256Lanes>)
+                       : reinterpret_cast<const void*>(&gf_apply<k, m, U, 3>);
   const void* fn_e = g_vec2 ? reinterpret_cast<const void*>(&gf_apply_vec<k, m, U, 2>)
                             : reinterpret_cast<const void*>(&lab::enc_early0<k, m>);
   const int per_e = g_vec2 ? 512 : 256;  // columns per workgroup of the variant
@@ -859,9 +918,9 @@ int skew_ab(int stripes, int kib, const std::vector<int>& skews, int rounds, int
   auto launch = [&](Slab& sl, const void* f = nullptr) {
     ApplyArgs args = sl.a;
     void* kargs[] = {&args};
-    const int per = f == fn_e ? per_e : 256;
-    CK(hipLaunchKernel(f ? f : fn, dim3(unsigned((sl.a.nvec + per - 1) / per), unsigned(stripes)), dim3(256), kargs,
-                       lds, nullptr));
+    const int per = f == fn_e ? per_e : PB;
+    CK(hipLaunchKernel(f ? f : fn, dim3(unsigned((sl.a.nvec + per - 1) / per), unsigned(stripes)),
+                       dim3(f == fn_e ? 256u : unsigned(PB)), kargs, f == fn_e ? lds_e : lds, nullptr));
   };
   for (int pass = 0; pass < (g_early0 ? 2 : 1); ++pass)
   for (auto& sl : slabs) {  // host spot check of stripe 0 and the last (pass 1: enc_early0)
