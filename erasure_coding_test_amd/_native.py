@@ -126,6 +126,12 @@ SIGNATURES = {
     "ecgpu_scrub_engine": (c_int, [c_void_p]),
     "ecgpu_scrub_destroy": (None, [c_void_p]),
     "ecgpu_scrub_blame_matrix": (c_int, [c_int, c_int, c_int_p, c_int_p, c_int_p]),
+    "ecgpu_multiplan_create": (c_void_p, [c_int, c_int, c_int, c_int_p, c_int]),
+    "ecgpu_multiplan_check": (c_int, [c_int, c_int, c_int, c_int, c_int_p, c_void_pp, c_void_pp, c_int64]),
+    "ecgpu_multiplan_bind": (c_int, [c_void_p, c_int, c_int_p, c_void_pp, c_void_pp, c_int64]),
+    "ecgpu_multiplan_launch": (c_int, [c_void_p, c_void_p]),
+    "ecgpu_multiplan_engine": (c_int, [c_void_p]),
+    "ecgpu_multiplan_destroy": (None, [c_void_p]),
     "ecgpu_recommended_shard_stride": (c_int64, [c_int64]),
     "ecgpu_recommended_shard_stride_km": (c_int64, [c_int64, c_int, c_int]),
     "ecgpu_pipeline_create": (c_void_p, [c_int, c_int, c_int_p, c_int64, c_int, c_int]),

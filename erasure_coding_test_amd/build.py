@@ -22,8 +22,10 @@ library carries content IDs (ecgpu_build_id):
      hipcc --version -- the identity a rocprofv3 PMC record of the bench's
      launches is valid for (profiles/summarize.py writes it, bench.py checks it)
   2  the same for the w = 16 / 32 kernels, 3 for the GF(2) packet kernels,
-     4 for the scrub kernels; each is its own kernel header and units plus
-     the shared device vocabulary gf_device.hpp, and no other family's kernels.
+     4 for the scrub kernels, 5 for the multi-map (rebuild) kernels
+     (maps_kernels.hpp, maps_spec.*, maps.hip); each is its own kernel header
+     and units plus the shared device vocabulary gf_device.hpp, and no other
+     family's kernels.
 """
 from __future__ import annotations
 
@@ -51,8 +53,8 @@ HOST_SRCS = ["gf_host.cpp", "matrix_host.cpp", "planner.cpp", "schedule_host.cpp
 # one translation unit per output-row count so the four compile in parallel
 HIP_UNITS = [(f, f + ".o", []) for f in ("ecgpu_runtime.hip", "plans.hip", "devices.hip", "contexts.hip",
                                            "host_memory.hip", "dispatch_w8.hip", "dispatch_wide.hip", "accum.hip",
-                                           "pipeline.hip", "packets.hip", "scrub.hip")] + [
-    (f"{t}.hip", f"{t}_r{r}.hip.o", [f"-DECGPU_SPEC_R={r}"]) for t in ("gf_spec", "wide_spec", "scrub_spec")
+                                           "pipeline.hip", "packets.hip", "scrub.hip", "maps.hip")] + [
+    (f"{t}.hip", f"{t}_r{r}.hip.o", [f"-DECGPU_SPEC_R={r}"]) for t in ("gf_spec", "wide_spec", "scrub_spec", "maps_spec")
     for r in (1, 2, 3, 4)]
 DROPIN_SRCS = ["jerasure_dropin.cpp", "jerasure_surface.cpp"]
 
@@ -95,6 +97,8 @@ KERNEL_FAMILIES = {
     "packets": (["gf_device.hpp", "gf_kernels_packets.hpp", "packets.hip"], ["ECGPU_PACKET"]),
     "scrub": (["gf_device.hpp", "scrub_kernels.hpp", "scrub_spec.hip", "scrub_spec.hpp", "scrub.hip"],
               ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_SCRUB_LATE"]),
+    "rebuild": (["gf_device.hpp", "maps_kernels.hpp", "maps_spec.hip", "maps_spec.hpp", "maps.hip"],
+                ["ECGPU_CAP", "ECGPU_BLOCKS_PER_CU", "ECGPU_NT"]),
 }
 
 
@@ -135,7 +139,7 @@ def toolchain(compiler: str) -> str:
 
 
 def build_ids() -> dict:
-    """{'build', 'kernels' (w = 8), 'wide', 'packets', 'scrub'}: 16-hex content IDs (see
+    """{'build', 'kernels' (w = 8), 'wide', 'packets', 'scrub', 'rebuild'}: 16-hex content IDs (see
     the module doc and KERNEL_FAMILIES)."""
     all_srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC)
                       if f.endswith((".hip", ".cpp", ".hpp")) and not f.startswith("diag_kernels"))
@@ -204,7 +208,7 @@ def build_native(verbose: bool = True) -> dict:
         s, o = os.path.join(CSRC, src), os.path.join(OBJ, src + ".o")
         extra = ([f'-DECGPU_BUILD_ID="{ids["build"]}"', f'-DECGPU_KERNEL_ID="{ids["kernels"]}"',
                   f'-DECGPU_WIDE_ID="{ids["wide"]}"', f'-DECGPU_PACKETS_ID="{ids["packets"]}"',
-                  f'-DECGPU_SCRUB_ID="{ids["scrub"]}"']
+                  f'-DECGPU_SCRUB_ID="{ids["scrub"]}"', f'-DECGPU_REBUILD_ID="{ids["rebuild"]}"']
                  if src == "capi_host.cpp" else [])
         cmd = [CXX] + CXXFLAGS + extra + ["-fvisibility=hidden", "-c", s, "-o", o]
         if _stale(o, [s] + include_closure(s), cmd):

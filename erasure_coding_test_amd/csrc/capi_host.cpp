@@ -34,7 +34,7 @@ ECGPU_API const char* ecgpu_last_error(void) { return rt::t_err.c_str(); }
 
 // Content IDs of this build (erasure_coding_test_amd/build.py): 0 the whole
 // library, 1 the w = 8 kernels and their dispatch, 2 the w = 16 / 32 ones,
-// 3 the GF(2) packet ones, 4 the scrub ones.
+// 3 the GF(2) packet ones, 4 the scrub ones, 5 the multi-map (rebuild) ones.
 #ifndef ECGPU_BUILD_ID
 #define ECGPU_BUILD_ID "unknown"
 #endif
@@ -50,12 +50,16 @@ ECGPU_API const char* ecgpu_last_error(void) { return rt::t_err.c_str(); }
 #ifndef ECGPU_SCRUB_ID
 #define ECGPU_SCRUB_ID "unknown"
 #endif
+#ifndef ECGPU_REBUILD_ID
+#define ECGPU_REBUILD_ID "unknown"
+#endif
 ECGPU_API const char* ecgpu_build_id(int what) {
   switch (what) {
     case 1: return ECGPU_KERNEL_ID;
     case 2: return ECGPU_WIDE_ID;
     case 3: return ECGPU_PACKETS_ID;
     case 4: return ECGPU_SCRUB_ID;
+    case 5: return ECGPU_REBUILD_ID;
     default: return ECGPU_BUILD_ID;
   }
 }

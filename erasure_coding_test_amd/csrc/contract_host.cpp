@@ -108,4 +108,21 @@ ECGPU_API int ecgpu_plan_check_buffers(int rows, int nsrc, int stripes, const ui
                   }));
 }
 
+// A multi-map bind (ecgpu_multiplan_bind calls this first): every stripe's
+// map index in range, then the plan contract above -- a multiplan is one
+// launch of rows <= 4 whichever map a stripe takes.
+ECGPU_API int ecgpu_multiplan_check(int rows, int nsrc, int nmaps, int stripes, const int* map_of,
+                                    const uint8_t* const* src_ptrs, uint8_t* const* dst_ptrs, int64_t size) {
+  using namespace ecgpu;
+  if (rows <= 0 || nsrc <= 0 || nmaps <= 0 || stripes < 0 || size < 0 ||
+      (stripes && (!map_of || !src_ptrs || !dst_ptrs)))
+    return rt::fail(ECGPU_ERR_ARG, "ecgpu_multiplan_check: bad arguments");
+  for (int st = 0; st < stripes; ++st)
+    if (map_of[st] < 0 || map_of[st] >= nmaps)
+      return rt::fail(ECGPU_ERR_ARG, "ecgpu_multiplan_bind: map_of[" + std::to_string(st) + "] = " +
+                                         std::to_string(map_of[st]) + " of stripe " + std::to_string(st) +
+                                         " is outside 0.." + std::to_string(nmaps - 1));
+  return ecgpu_plan_check_buffers(rows, nsrc, stripes, src_ptrs, dst_ptrs, size);
+}
+
 }  // extern "C"

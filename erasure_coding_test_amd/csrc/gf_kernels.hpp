@@ -37,7 +37,8 @@
 //     the units that instantiate its kernels or take their address:
 //     gf_kernels_w8.hpp (gf_spec.hip, dispatch_w8.hip), gf_kernels_wide.hpp
 //     (wide_spec.hip, dispatch_wide.hip), gf_kernels_packets.hpp
-//     (packets.hip), scrub_kernels.hpp (scrub_spec.hip, scrub.hip).  The
+//     (packets.hip), scrub_kernels.hpp (scrub_spec.hip, scrub.hip),
+//     maps_kernels.hpp (maps_spec.hip, maps.hip; all templates).  The
 //     non-template kernels are compiled once, in the unit that launches them
 //     (gf_apply_bytes in dispatch_w8.hip, the scrub byte kernels in scrub.hip).
 //  3. diag_kernels_w8.hpp -- measurement-only forms, libecgpu_diag.so and

@@ -12,6 +12,7 @@
 //   pipeline.hip       host-memory pipelines and multi-device groups
 //   packets.hip        GF(2) bit-matrix / schedule coding
 //   scrub.hip          stripe scrub: fused parity verify with shard blame
+//   maps.hip           multi-map plans: a coefficient matrix per stripe
 // Everything here lives in ecgpu::rt with hidden visibility: the shared
 // library exports only the ECGPU_API functions.
 #pragma once
@@ -148,6 +149,9 @@ int unit_variant(const std::vector<uint32_t>& coef, int K, int r0, int R);
 unsigned residency_lds_bytes(int device, int streams, unsigned static_bytes = 0, int lanes = ecgpu::dev::kBlock);
 int residency_waves_per_cu(int streams, int lanes);  // the rule behind it, in waves per CU
 bool cap_for(int K, int R, int mul_terms, bool seq = false);  // seq: the sequential R >= 3 body of gf_apply
+// the tables of one coefficient: 2-bit PERM (q), 3-bit-slice (p3, kP3Words
+// dwords) and nibble (nib, 32 bytes)
+void build_tables(int c, ecgpu::dev::u32x4* q, uint32_t* p3, uint8_t* nib);
 
 // ---- plans (plans.hip) --------------------------------------------------------
 // A store-policy request clamped to the policies the kernels have (gf_spec.hpp).

@@ -6,8 +6,9 @@ table of device pointers for many stripes; ``launch`` enqueues one fused
 verify pass (the k + m shards read once, nothing written for a clean stripe)
 plus the blame of the bad stripes, asynchronously on a HIP stream and
 graph-capturable like :class:`~.plan.StripePlan`.  ``results`` reads the
-per-stripe verdicts; ``repair`` hands each stripe with exactly one suspect to
-a :class:`~.plan.DecodePlan` and scrubs again.  w = 8 and device memory only.
+per-stripe verdicts; ``repair`` hands the stripes with exactly one suspect to
+one :class:`~.rebuild.RebuildPlan` and scrubs again.  w = 8 and device memory
+only.
 """
 from __future__ import annotations
 
@@ -18,7 +19,7 @@ import torch
 
 from . import _native as N
 from ._buffers import addr
-from .plan import DecodePlan
+from .rebuild import RebuildPlan
 
 SCRUB_MAX_M = 8
 _NO_POSITION = 2**64 - 1
@@ -103,7 +104,8 @@ class ScrubPlan:
 
     def repair(self, shards: Sequence[Sequence], size: int):
         """Scrub, rebuild every stripe that has exactly one suspect shard (one
-        DecodePlan per suspect, over just its stripes), scrub again.
+        RebuildPlan: a single launch whichever shard each stripe lost), scrub
+        again.
 
         Returns ``(repaired, unrepaired, results_after)``: repaired = [(stripe,
         shard)] whose stripe is clean afterwards, unrepaired = the stripes
@@ -111,20 +113,13 @@ class ScrubPlan:
         second scrub did not confirm)."""
         self.bind_stripes(shards, size)
         self.launch()
-        groups = {}
-        for s, r in enumerate(self.results()):
-            if not r.clean and len(r.suspects) == 1:
-                groups.setdefault(r.suspects[0], []).append(s)
-        plans = []
-        for shard, stripes in sorted(groups.items()):
-            plan = DecodePlan(self.k, self.m, self.matrix, [shard], device=self.device)
-            plan.bind_stripes([shards[s] for s in stripes], size).launch()
-            plans.append(plan)
+        tried = {s: r.suspects[0] for s, r in enumerate(self.results()) if not r.clean and len(r.suspects) == 1}
+        rebuild = RebuildPlan(self.k, self.m, self.matrix, device=self.device)
+        if tried:
+            rebuild.bind_stripes(shards, [[tried[s]] if s in tried else [] for s in range(len(shards))], size).launch()
         self.launch()
-        after = self.results()  # waits for the stream: the decode plans are done
-        for plan in plans:
-            plan.close()
-        tried = {s: shard for shard, stripes in groups.items() for s in stripes}
+        after = self.results()  # waits for the stream: the rebuild is done
+        rebuild.close()
         repaired = [(s, tried[s]) for s in sorted(tried) if after[s].clean]
         unrepaired = [s for s, r in enumerate(after) if not r.clean]
         return repaired, unrepaired, after

@@ -71,7 +71,8 @@ ECGPU_API const char* ecgpu_version(void);
 /* Content IDs of the built library (16 hex digits): what = 0 the whole
  * library, 1 the w = 8 kernels and their dispatch (the identity a rocprofv3
  * PMC record of the bench's launches is valid for), 2 the w = 16 / 32
- * kernels, 3 the GF(2) packet kernels, 4 the scrub kernels. */
+ * kernels, 3 the GF(2) packet kernels, 4 the scrub kernels, 5 the multi-map
+ * (rebuild) kernels. */
 ECGPU_API const char* ecgpu_build_id(int what);
 ECGPU_API const char* ecgpu_last_error(void);         /* thread-local message */
 /* Tuning / A-B switches (knobs.hpp lists them: the residency cap, engines,
@@ -340,6 +341,56 @@ ECGPU_API void ecgpu_scrub_destroy(ecgpu_scrub* s);
 /* Host only: pivots[k] (-1 for an all-zero column) and ratios[m*k] of the
  * blame test above. */
 ECGPU_API int ecgpu_scrub_blame_matrix(int k, int m, const int* matrix, int* pivots, int* ratios);
+
+/* ------------------- multi-map plans: a coefficient matrix per stripe ---- */
+/* A plan applies one matrix to every stripe of a launch; a rebuild does not
+ * look like that.  Under rotated placement a failed device held shard
+ * s mod (k + m) of stripe s, and a scrub hands back "stripe 17 lost shard 3,
+ * stripe 18 lost shard 12": many erasure patterns, a handful of stripes each.
+ * A multiplan holds `nmaps` coefficient matrices of one common rows x nsrc
+ * shape (tables of all maps uploaded once) and picks a map per stripe in ONE
+ * launch:
+ *     dst[s][r] = XOR_j coefs[map_of[s]][r][j] * src[s][j]   over `size` bytes.
+ * Plan-style: create, bind (blocking; the pointer tables and map_of go up
+ * together), launch (asynchronous on a hipStream_t, graph-capturable once
+ * bound, stripes batched 65535 at a time).  Patterns whose fused decode maps
+ * (ecgpu_decode_plan) share a shape -- every single-shard loss of a scheme,
+ * for one -- go into one multiplan; the Python RebuildPlan groups them.
+ *
+ * Buffers: device pointers only, under the contract of
+ * ecgpu_plan_check_buffers(rows, nsrc, ...): an output may be identical to a
+ * source of its own stripe, any other byte shared with an output is rejected.
+ * Shapes with nsrc <= 16 whose pointers are all 16-B aligned run the
+ * specialised 16-B-column kernel (and a byte kernel for the tail size % 16);
+ * every other shape or alignment runs the byte kernel alone
+ * (ecgpu_multiplan_engine).  Zero and unit coefficients are table contents:
+ * no map's unit structure is compiled in.
+ *
+ * Out of scope: w = 16 / 32; the GF(2) packet codes; host-memory shards and
+ * the CPU executor (a multiplan never runs on the CPU: ecgpu_cpu_call_count
+ * and ecgpu_fallback_count do not move); ecgpu_plan_set_kernel (there is no
+ * LDS engine here; the store policy is ECGPU_NT's at creation); the drop-in
+ * libjerasure_amd.so, since the reference has no such call. */
+typedef struct ecgpu_multiplan ecgpu_multiplan;
+/* NULL (ecgpu_last_error) unless 1 <= rows <= 4, nsrc >= 1, nmaps >= 1 and
+ * coefs ([nmaps][rows][nsrc], row-major per map) is not NULL -- checked before
+ * any HIP call.  device < 0: the current device.  The table upload is
+ * asynchronous, like ecgpu_plan_create's. */
+ECGPU_API ecgpu_multiplan* ecgpu_multiplan_create(int rows, int nsrc, int nmaps, const int* coefs, int device);
+/* Host only (ecgpu_multiplan_bind runs it first): ECGPU_ERR_ARG, naming the
+ * stripe, for a map_of entry outside 0..nmaps-1; then the buffer contract of
+ * ecgpu_plan_check_buffers(rows, nsrc, ...), unchanged. */
+ECGPU_API int ecgpu_multiplan_check(int rows, int nsrc, int nmaps, int stripes, const int* map_of,
+                                    const uint8_t* const* src_ptrs, uint8_t* const* dst_ptrs, int64_t size);
+ECGPU_API int ecgpu_multiplan_bind(ecgpu_multiplan* p, int stripes, const int* map_of /* [stripes], 0..nmaps-1 */,
+                                   const uint8_t* const* src_ptrs /* [s*nsrc+j] */,
+                                   uint8_t* const* dst_ptrs /* [s*rows+r] */, int64_t size);
+/* Asynchronous; a no-op for stripes == 0 or size == 0. */
+ECGPU_API int ecgpu_multiplan_launch(ecgpu_multiplan* p, void* stream);
+/* 0: the specialised vector kernel (+ byte tail) runs for the current binding
+ * (before a bind: for the shape), 1: the byte kernel only. */
+ECGPU_API int ecgpu_multiplan_engine(ecgpu_multiplan* p);
+ECGPU_API void ecgpu_multiplan_destroy(ecgpu_multiplan* p);
 
 /* ECX-style incremental parity accumulation (ecx_datanode_main.cpp:680-735)
  * with the m accumulators resident in HBM.  Source blocks arrive one at a
